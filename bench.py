@@ -18,9 +18,18 @@ are resident in HBM before the timed region.
                  == cpu_spmv.cpp OmpMergeCsrmv) compiled from /root/reference into oracle/_ref,
                  else the oracle port; host cores, ~10 s on matrix #0 (rank 0, N = 1 only)
 
-Extra fields: the scattered-band stress shape, CG iterations/s for configs[3] (single CG,
-parabolic_fem shape) and configs[4] (8-RHS block CG, nlpkkt120 size; at N > 1 row-sharded over
-all ranks with RCCL halo exchange + dot all-reduces).
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the
+line with the headline and the roofline of the timed launches themselves.  Everything else is behind
+--full: cpu_baseline, the hot single matrix, the measured read ceiling, the merge-path plans, the
+scattered-band stress shape, the perturbed pwtk, SpMM and window shapes, CG iterations/s for
+configs[3] (single CG, parabolic_fem shape) and configs[4] (8-RHS block CG, nlpkkt120 size; at
+N > 1 row-sharded over all ranks with RCCL halo exchange + dot all-reduces) and, at N > 1, the
+local-SpMV roofline; --no-cpu / --no-cg / --no-extras trim a --full run.  `--only LEG` runs one side
+measurement alone, with or without --full.
+
+--dump-outputs DIR writes, after the timed steps, the y vector of every matrix of the batch as the
+last timed step left it: DIR/y<i>.npy, float64 (1.7 MB each).  The inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
 
 Launch: `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts its own N
 ranks -- before it imports mspmv or touches a GPU, the parent runs `python -m torch.distributed.run
@@ -34,7 +43,7 @@ Multi-GPU (--gpus N via torch.distributed.run; run_sharded_headline): weak scali
 exchange step -- each matrix of the batch is ONE FEM-blocked matrix of N x 217,918 rows, sharded by
 merge-path row blocks; every rank generates only its pwtk-sized block, and each SpMV exchanges the
 halo rows of x over RCCL (send/recv, xGMI) while the block interior is multiplied.  value = all
-ranks' flops / max-over-ranks time; roofline = the per-rank local SpMV (no exchange).  gloo
+ranks' flops / max-over-ranks time; roofline (--full) = the per-rank local SpMV (no exchange).  gloo
 carries the barrier, the max-over-ranks reductions and the RCCL ids.  A watchdog turns a hang of
 the collective part into exit 3 with the line printed.
 """
@@ -780,9 +789,10 @@ def run_sharded_headline(d, dev, args):
             dc.spmm_dev(xp, dy, 1, sync=False)
     for dc in dcs:
         dc.sync()
-    # per-rank SpMV alone (no exchange): the head / interior / tail launches back to back
-    loc_ms = float(np.mean([dc.time_local(dy, 1, 100) for dc, dy in zip(dcs, dys)]))
-    loc_ms = d.max(loc_ms)
+    loc_ms = None
+    if args.full:  # per-rank SpMV alone (no exchange): the head / interior / tail launches back to back
+        loc_ms = float(np.mean([dc.time_local(dy, 1, 100) for dc, dy in zip(dcs, dys)]))
+        loc_ms = d.max(loc_ms)
     d.barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -793,10 +803,10 @@ def run_sharded_headline(d, dev, args):
     el = time.perf_counter() - t0
     d.barrier()
     el = d.max(el)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, d, dys, [hi - lo] * len(dys))
     inf = infos[0]
-    m_loc, n_ext = inf["n_own"], inf["n_own"] + inf["n_halo"]
-    bytes_local = 12 * nnz_loc + 4 * (m_loc + 1) + 8 * n_ext + 8 * m_loc
-    achieved = bytes_local / (loc_ms * 1e-3) / 1e9
+    m_loc = inf["n_own"]
     value = 2.0 * NNZ * args.batch * args.steps / el / 1e9
     result = {
         "metric": METRIC, "value": round(value, 2), "unit": "GFLOP/s", "n_gpus": world,
@@ -810,16 +820,30 @@ def run_sharded_headline(d, dev, args):
                    "parallelism": f"row-block sharding over {world} GPUs: RCCL halo exchange of x (send/recv over "
                                   f"xGMI) overlapped with the block interior"},
         "halo": {"rows": inf["n_halo"], "rows_sent": inf["n_send"], "bytes_per_exchange": 8 * inf["n_halo"]},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
-                     "kernel": "local SpMV (head + interior + tail launches)", "bytes_per_launch": bytes_local,
-                     "kernel_ms": round(loc_ms, 5),
-                     "note": "per-rank local SpMV without the exchange, HIP events, max over ranks; algorithmic "
-                             "bytes 12 nnz + 4 (m+1) + 8 (n_own + n_halo) + 8 m of the rank's block"},
     }
+    if loc_ms is not None:
+        n_ext = inf["n_own"] + inf["n_halo"]
+        bytes_local = 12 * nnz_loc + 4 * (m_loc + 1) + 8 * n_ext + 8 * m_loc
+        achieved = bytes_local / (loc_ms * 1e-3) / 1e9
+        result["roofline"] = {
+            "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
+            "kernel": "local SpMV (head + interior + tail launches)", "bytes_per_launch": bytes_local,
+            "kernel_ms": round(loc_ms, 5),
+            "note": "per-rank local SpMV without the exchange, HIP events, max over ranks; algorithmic "
+                    "bytes 12 nnz + 4 (m+1) + 8 (n_own + n_halo) + 8 m of the rank's block"}
     for dc in dcs:
         dc.close()
     return result
+
+
+def dump_outputs(path, d, dys, rows):
+    """--dump-outputs: the y vectors the last timed step left in HBM (rows[i] doubles each), one .npy per matrix
+    of the batch; 1.7 MB each at the pwtk shape."""
+    os.makedirs(path, exist_ok=True)
+    rank = f".rank{d.rank}" if d.world > 1 else ""
+    for i, (dy, m) in enumerate(zip(dys, rows)):
+        np.save(os.path.join(path, f"y{i}{rank}.npy"), dy.download((m,)))
 
 
 def main():
@@ -845,7 +869,20 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="launch check only: every rank joins the gloo group and reports WORLD_SIZE / RANK; "
                          "no GPU is touched")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything else the benchmark measures: the CPU baselines, the "
+                         "side shapes (hot single matrix, merge-path plans, scattered band, perturbed pwtk, SpMM, "
+                         "window shapes, measured read ceiling), the CG legs and, at N > 1, the local-SpMV roofline; "
+                         "--no-cpu / --no-cg / --no-extras then trim it.  Without --full only the headline is run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the y vector of every matrix of the batch as the last timed "
+                         "step left it to DIR/y<i>.npy (float64; at N > 1 each rank writes its rows as "
+                         "DIR/y<i>.rank<r>.npy)")
     args = ap.parse_args()
+    # a plain run measures the headline only; --only legs keep their own switches
+    extras = args.full and not args.no_extras
+    do_cpu = args.full and not args.no_cpu
+    do_cg = args.full and not args.no_cg
 
     d = Dist(args.gpus)
     if args.dry_run:
@@ -861,17 +898,17 @@ def main():
         return
     if args.only:
         dev = d.local if args.device is None else args.device
-        do_cpu = not args.no_cpu
+        leg_cpu = not args.no_cpu
         if args.only == "merge_path_generic":
             r = run_merge_path_generic(dev)
         elif args.only == "window_shapes":
             r = run_window_shapes(dev)
         elif args.only == "spmm16":
-            r = run_spmm16(dev, min(args.cpu_seconds, 5.0), do_cpu)
+            r = run_spmm16(dev, min(args.cpu_seconds, 5.0), leg_cpu)
         elif args.only == "spmv_shapes":
-            r = run_spmv_shapes(dev, min(args.cpu_seconds, 3.0), do_cpu)
+            r = run_spmv_shapes(dev, min(args.cpu_seconds, 3.0), leg_cpu)
         elif args.only == "cg_single":
-            r = run_cg_single(dev, min(args.cpu_seconds, 10.0), do_cpu)
+            r = run_cg_single(dev, min(args.cpu_seconds, 10.0), leg_cpu)
         elif args.only == "pwtk_perturbed":
             r = run_pwtk_perturbed(dev)
         else:
@@ -919,13 +956,15 @@ def main():
         d.barrier()
         el = d.max(el)
         kern_ms = d.max(kern_ms)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, d, dys, [a.num_rows for a in mats])
 
         flops = 2.0 * a0.num_nonzeros * args.batch * args.steps * d.world
         value = flops / el / 1e9
         bytes_launch = spmv_bytes(a0.num_rows, a0.num_cols, a0.num_nonzeros)
         achieved = bytes_launch / (kern_ms * 1e-3) / 1e9
         hot_ms = hot_kern = None
-        if not args.no_extras:
+        if extras:
             hot_ms, hot_kern, _ = mspmv.time_spmm_batch(gs[:1], dxs[:1], dys[:1], 1, 200)
         kname = gs[0].kernel_name()
         traffic, traffic_src = pmc_traffic(kname, bytes_launch)
@@ -952,7 +991,7 @@ def main():
             "reference_effective_GBps": round(ref_eff, 1),
             "setup_ms": round(gs[0].setup_ms, 2),
         }
-        if not args.no_extras:  # the practical ceiling beside the spec peak
+        if extras:  # the practical ceiling beside the spec peak
             rd = mspmv.time_stream_read(dev, 1 << 30, 20)
             result["roofline"]["measured_read_GBps"] = round(rd, 1)
             result["roofline"]["frac_of_measured_read"] = round(achieved / rd, 4) if rd > 0 else None
@@ -960,7 +999,7 @@ def main():
                                                         "one contiguous slice per workgroup, 4 workgroups per CU, "
                                                         "20 passes, HIP events (the best of the read shapes in "
                                                         "tools/read_ceiling.hip)")
-        if not args.no_extras:
+        if extras:
             # north_star's figure is merge-based CsrMV: the same batch on the merge-path tile plan (node blocks
             # in registers, tiles cut at 2,048 merge items) beside the default run-balanced plan, and on the
             # generic merge-path tiles (no node blocks) in a child process
@@ -979,7 +1018,7 @@ def main():
         for g in gs:
             g.close()
 
-        if d.rank == 0 and not args.no_extras:  # stress shape: columns scattered one per band slice (x gathers hit a new line each)
+        if d.rank == 0 and extras:  # stress shape: columns scattered one per band slice (x gathers hit a new line each)
             # a batch of 4 (> the Infinity Cache, as the headline); the plain SpMV takes the column-slab
             # plan here by default (line-bound gathers: mspmv_slab.hip)
             scs = [mspmv.CsrMatrix.synth_banded(PWTK["m"], PWTK["nnz"], 10000, seed=77 + i) for i in range(4)]
@@ -1001,13 +1040,13 @@ def main():
             for b_ in sbx + sby:
                 b_.free()
 
-        if d.rank == 0 and not args.no_extras:
+        if d.rank == 0 and extras:
             result["spmv_pwtk_perturbed"] = run_pwtk_perturbed(dev)
-            result["spmm16"] = run_spmm16(dev, min(args.cpu_seconds, 5.0), d.world == 1 and not args.no_cpu)
-            result["spmv_shapes"] = run_spmv_shapes(dev, min(args.cpu_seconds, 3.0), d.world == 1 and not args.no_cpu)
+            result["spmm16"] = run_spmm16(dev, min(args.cpu_seconds, 5.0), d.world == 1 and do_cpu)
+            result["spmv_shapes"] = run_spmv_shapes(dev, min(args.cpu_seconds, 3.0), d.world == 1 and do_cpu)
             result["window_shapes"] = run_window_shapes(dev)
 
-        if d.rank == 0 and d.world == 1 and not args.no_cpu:
+        if d.rank == 0 and d.world == 1 and do_cpu:
             y_cpu, cb = cpu_baseline(a0, xs[0], args.cpu_seconds)
             result["cpu_baseline"] = cb
             with mspmv.GpuCsr(a0, device=dev) as g:
@@ -1015,10 +1054,10 @@ def main():
             rel = float(np.max(np.abs(y_gpu - y_cpu) / np.maximum(np.abs(y_cpu), 1e-300)))
             result["cpu_baseline"]["gpu_vs_cpu_max_rel_diff"] = rel
             result["speedup_vs_cpu"] = round(value / cb["value"], 1)
-    if not args.no_cg:
+    if do_cg:
         try:
             if d.world == 1:
-                result["cg_single"] = run_cg_single(dev, min(args.cpu_seconds, 10.0), not args.no_cpu)
+                result["cg_single"] = run_cg_single(dev, min(args.cpu_seconds, 10.0), do_cpu)
             result["cg_multi"], large = run_cg_multi(d, dev)
             if large:
                 result["spmv_nlpkkt120_size"] = large
@@ -1029,7 +1068,7 @@ def main():
     if guard:
         if not guard.finish():  # the watchdog fired meanwhile and owns the exit
             return
-    if d.world > 1 and not args.no_cpu:
+    if d.world > 1 and do_cpu:
         # north_star: the reference CPU path timed on the host cores "in the same run" at every N;
         # rank 0, after the GPU legs (the other ranks wait at the barrier below)
         if d.rank == 0:

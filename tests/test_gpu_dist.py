@@ -228,8 +228,8 @@ def test_bench_sharded_headline_world1(tmp_path):
     import json
     import subprocess
     env = dict(os.environ, MSPMV_BENCH_SHARDED="1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--no-cg",
-                        "--no-cpu"], env=env, capture_output=True, text=True, timeout=300)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--full",
+                        "--no-cg", "--no-cpu"], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["scaling"] == "weak" and line["value"] > 100

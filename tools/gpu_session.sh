@@ -33,7 +33,7 @@ for s in $STEPS; do
         timeout -k 10 900 python -m pytest tests -m gpu -q -p no:cacheprovider -rf >"$OUT/pytest_gpu.log" 2>&1
         rc=$?; echo "pytest rc=$rc"; tail -25 "$OUT/pytest_gpu.log"; stop_unless_ok $rc tests ;;
     bench)
-        timeout -k 10 600 python bench.py >"$OUT/bench.json" 2>"$OUT/bench.err"
+        timeout -k 10 600 python bench.py --full >"$OUT/bench.json" 2>"$OUT/bench.err"
         rc=$?; echo "bench rc=$rc"; cat "$OUT/bench.json"; tail -5 "$OUT/bench.err"; stop_unless_ok $rc bench ;;
     prof)
         timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o bench \
