@@ -22,7 +22,7 @@
 //     ahead (nobody can still be reading it: every workgroup is within one iteration of every
 //     other).  Every spin is bounded: a timeout raises an abort word that every poller checks,
 //     and the solve reports MSPMV_ERR_STALL instead of hanging the GPU.
-// Semantics are the pipelined CG's (mspmv_kernels.hip k_cg1_*): x = 0, r = p = b, b_norm =
+// Semantics are the pipelined CG's (mspmv_cg_passes.hip k_cg1_*): x = 0, r = p = b, b_norm =
 // ||b|| (1 if 0), per iteration alpha = rs / p.Ap (a non-finite alpha stops before x and r
 // change: MSPMV_ERR_BREAKDOWN), x += alpha p, r += (-alpha) Ap, hist[k] = sqrt(rs_new) / b_norm,
 // stop when it is < tol (iterations = k + 1), beta = rs_new / rs.  Row sums are sequential in CSR

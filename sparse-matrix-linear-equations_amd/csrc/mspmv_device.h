@@ -1,5 +1,5 @@
-// Device helpers shared by the tile kernels (mspmv_kernels.hip) and the column-slab SpMV
-// (mspmv_slab.hip): agent-scope stores and loads, the XCD-contiguous tile mapping, and the closing of
+// Device helpers shared by the tile kernels (mspmv_kernels.hip), the CG passes (mspmv_cg_passes.hip)
+// and the column-slab SpMV (mspmv_slab.hip): agent-scope stores and loads, the XCD-contiguous tile mapping, and the closing of
 // rows split between tiles.  Included by HIP sources only.
 #pragma once
 #include "mspmv_internal.h"

@@ -387,8 +387,8 @@ k_spmm_dia(DiaArgs a)
 }
 
 // ---- pipelined single-RHS CG on the offset windows -----------------------------------------------
-// The two-kernel pipelined CG (mspmv_kernels.hip: [SpMV MODE 1] -> [k_cg1_update]) with its SpMV on the
-// windows instead of the merge tiles, for the single-RHS matrices the register-resident kernel does not
+// The two-kernel pipelined CG ([SpMV MODE 1, mspmv_kernels.hip] -> [k_cg1_update, mspmv_cg_passes.hip]) with
+// its SpMV on the windows instead of the merge tiles, for the single-RHS matrices the register-resident kernel does not
 // hold: a 27-point stencil of pwtk's size runs the plain product in 20 us on the windows against 60 us on
 // the tiles, and the tiles' CG form took 78 us (r06f).  One launch of iteration k:
 //  * head: every workgroup sums the update's <= kUpdateMaxBlocks r.r partials in one fixed order
@@ -579,10 +579,9 @@ hipError_t launch_cg1_dia(mspmv_handle_s *h, const TilePlan &plan, const double 
     c.hist_cap = h->hist_cap;
     *nslots = a.groups;
     const dim3 grid((unsigned)a.groups), block(kDiaThreads);
-    if (stream_nt(h))
-        hipLaunchKernelGGL((k_cg1_dia<true>), grid, block, 0, h->stream, a, c);
-    else
-        hipLaunchKernelGGL((k_cg1_dia<false>), grid, block, 0, h->stream, a, c);
+    dispatch_bool(stream_nt(h), [&](auto ntc) {
+        hipLaunchKernelGGL((k_cg1_dia<decltype(ntc)::value>), grid, block, 0, h->stream, a, c);
+    });
     return hipGetLastError();
 }
 
@@ -1061,16 +1060,13 @@ template <int L>
 static void dia_launch_L(const DiaArgs &a, hipStream_t s, bool nt)
 {
     const dim3 grid((unsigned)a.groups), block(kDiaThreads);
-    if (a.partials) {
-        if (nt)
-            hipLaunchKernelGGL((k_spmm_dia<L, true, true>), grid, block, 0, s, a);
+    dispatch_bool(nt, [&](auto ntc) {
+        constexpr bool NT = decltype(ntc)::value;
+        if (a.partials)
+            hipLaunchKernelGGL((k_spmm_dia<L, NT, true>), grid, block, 0, s, a);
         else
-            hipLaunchKernelGGL((k_spmm_dia<L, false, true>), grid, block, 0, s, a);
-    } else if (nt) {
-        hipLaunchKernelGGL((k_spmm_dia<L, true>), grid, block, 0, s, a);
-    } else {
-        hipLaunchKernelGGL((k_spmm_dia<L, false>), grid, block, 0, s, a);
-    }
+            hipLaunchKernelGGL((k_spmm_dia<L, NT>), grid, block, 0, s, a);
+    });
 }
 
 hipError_t launch_dia(mspmv_handle_s *h, const TilePlan &plan, const double *d_X, double *d_Y, int L, int ld,
@@ -1101,15 +1097,10 @@ hipError_t launch_dia(mspmv_handle_s *h, const TilePlan &plan, const double *d_X
     a.ld = ld > 0 ? ld : L;
     const bool nt = stream_nt(h);
     hipStream_t s = stream ? stream : h->stream;
-    switch (L) {
-    case 1: dia_launch_L<1>(a, s, nt); break;
-    case 2: dia_launch_L<2>(a, s, nt); break;
-    case 4: dia_launch_L<4>(a, s, nt); break;
-    case 8: dia_launch_L<8>(a, s, nt); break;
-    case 16: dia_launch_L<16>(a, s, nt); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_L(L, [&](auto Lc) {
+        dia_launch_L<decltype(Lc)::value>(a, s, nt);
+        return hipGetLastError();
+    });
 }
 
 std::string dia_kernel_name(const mspmv_handle_s *h, int L)

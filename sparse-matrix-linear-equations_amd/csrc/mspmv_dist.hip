@@ -772,7 +772,7 @@ static mspmv_status dist_cg_native(mspmv_dist d, const double *d_B_own, double *
     }
     D_ST(ensure_buffers(d, L, nblk, std::max({plan->num_tiles, dlocal ? dlocal->num_tiles : 0, toff[3]}), cap));
     hipStream_t s = d->local->stream;
-    DistVecArgs va{};
+    CgVecArgs va{};  // (lazy_x, rev: the single-GPU split CG's, 0 here)
     va.n_elems = elems;
     va.x = d_X_own;
     va.r = d->d_r;
@@ -804,19 +804,19 @@ static mspmv_status dist_cg_native(mspmv_dist d, const double *d_B_own, double *
     // fold tickets: zeroed at every solve's start (a solve that stopped early or faulted may leave some raised)
     D_HIP(hipMemsetAsync(d->d_gtickets, 0, sizeof(unsigned) * d->gtickets_cap, s));
     {
-        DistVecArgs a = va;
+        CgVecArgs a = va;
         a.p = d_B_own;
         a.red_out = rr;
-        D_HIP(launch_dist_vec_mirror(0, a, L, nblk, nullptr, s));
+        D_HIP(launch_dist_vec(CgVecPass::InitPartials, a, L, nblk, nullptr, s));
         D_NCCL(ncclAllReduce(rr, rr, L, ncclFloat64, ncclSum, d->comm, s));
         a.red_in = rr;
-        D_HIP(launch_dist_vec_mirror(1, a, L, 1, nullptr, s));
+        D_HIP(launch_dist_vec(CgVecPass::InitFinish, a, L, 1, nullptr, s));
     }
     if (poison & MSPMV_POISON_FILL)  // test hook: the iterations' folds meet dirty tickets (after the init's)
         D_HIP(hipMemsetD32Async((hipDeviceptr_t)d->d_gtickets, (int)d->poison_value, d->gtickets_cap, s));
     auto iteration = [&]() -> mspmv_status {
-        DistVecArgs a = va;
-        D_HIP(launch_dist_vec_mirror(2, a, L, nblk, d->d_pext, s));       // p = r + beta p
+        CgVecArgs a = va;
+        D_HIP(launch_dist_vec(CgVecPass::PUpdate, a, L, nblk, d->d_pext, s));  // p = r + beta p
         if (!split) {
             D_ST(halo_exchange(d, L, d->d_ctrl));                           // p halo rows
             if (dlocal) {
@@ -850,9 +850,9 @@ static mspmv_status dist_cg_native(mspmv_dist d, const double *d_B_own, double *
         D_NCCL(ncclAllReduce(pAp, pAp, L, ncclFloat64, ncclSum, d->comm, s));
         a.red_in = pAp;
         a.red_out = rr;
-        D_HIP(launch_dist_vec_mirror(3, a, L, nblk, nullptr, s));          // x, r, local r.r
+        D_HIP(launch_dist_vec(CgVecPass::XrUpdate, a, L, nblk, nullptr, s));   // x, r, local r.r
         D_NCCL(ncclAllReduce(rr, rr, L, ncclFloat64, ncclSum, d->comm, s));
-        D_HIP(launch_dist_vec_mirror(4, a, L, 1, nullptr, s));             // stop test, beta
+        D_HIP(launch_dist_vec(CgVecPass::Finish, a, L, 1, nullptr, s));        // stop test, beta
         return MSPMV_OK;
     };
     int iterations_enqueued = 0;

@@ -9,7 +9,7 @@
 //     1e-3, then x10 per attempt, 20 attempts (:150-173, :213-225).
 // The reference factorizes sequentially on the CPU; this is setup, run once, and stays on the
 // host the same way.  The two triangular solves it feeds run on the GPU every iteration
-// (k_trsv, sync-free, mspmv_kernels.hip).
+// (k_trsv_tagged, sync-free, mspmv_cg_passes.hip).
 #include "mspmv.h"
 
 #include <cmath>

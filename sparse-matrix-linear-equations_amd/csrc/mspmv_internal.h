@@ -1,11 +1,13 @@
-// mspmv_internal.h -- shared between the HIP kernels (mspmv_kernels.hip) and the C-ABI
-// implementation (mspmv_api.hip).  Not installed; the public boundary is include/mspmv.h.
+// mspmv_internal.h -- shared between the HIP translation units (the kernels files and the C-ABI
+// implementation, mspmv_api.hip).  Not installed; the public boundary is include/mspmv.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <map>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "mspmv.h"
@@ -390,12 +392,15 @@ std::string dia_kernel_name(const mspmv_handle_s *h, int L);
 // p.Ap partial per workgroup into h->d_partials; *nslots = that count, for k_cg1_update's consumer level.
 hipError_t launch_cg1_dia(mspmv_handle_s *h, const TilePlan &plan, const double *rp_old, double *rp_new, double *d_x,
                           int parity, int nblk, double tol, int *nslots);
+// ... and on the merge-path tiles of `plan` (mspmv_kernels.hip, k_spmv_tile MODE 1): one p.Ap partial per tile.
+hipError_t launch_cg1_tile(mspmv_handle_s *h, const TilePlan &plan, const double *rp_old, double *rp_new, double *d_x,
+                           int parity, int nblk, double tol, int *nslots);
 bool dia_spmm_enabled();  // the L-wide products on the windows too unless MSPMV_DIA_SPMM=0 (mspmv_api.hip)
 // The handle's offset-window plan for width L (decided on first use), or null (mspmv_api.hip)
 mspmv_status dia_plan_for(mspmv_handle_s *h, int L, const TilePlan **out);
-bool dia_dot_fused();     // the window SpMM takes p.Ap in its dot mode unless MSPMV_DIA_DOT=0 (mspmv_kernels.hip)
+bool dia_dot_fused();     // the window SpMM takes p.Ap in its dot mode unless MSPMV_DIA_DOT=0 (mspmv_cg_passes.hip)
 
-// ---- launchers (mspmv_kernels.hip) --------------------------------------------------
+// ---- launchers (mspmv_kernels.hip; the CG pieces below: mspmv_cg_passes.hip) ---------
 void set_error(const std::string &msg);
 hipError_t launch_merge_coords(const int *d_row_offsets, int m, int nnz, long long diag_step, int num_parts,
                                int2 *d_out, hipStream_t s);
@@ -439,9 +444,10 @@ hipError_t launch_spmm(mspmv_handle_s *h, const TilePlan &plan, const double *d_
 // dst[i][j] = (j < cols ? src[i][j] : 0) for i < rows, j < dcols (row-major, strides lds / ldd).
 hipError_t launch_panel_copy(const double *src, int lds, double *dst, int ldd, long long rows, int cols, int dcols,
                              hipStream_t s);
-// ld: panel leading dimension in doubles (0: L, whole panels)
+// ld: panel leading dimension in doubles (0: L, whole panels); ctrl (CG): the product returns at once
+// when ctrl->done is set and raises its faults in ctrl->fault
 hipError_t launch_spmm_tile_only(mspmv_handle_s *h, const TilePlan &plan, const double *d_X, double *d_Y, int L,
-                                 int ld = 0);
+                                 int ld = 0, CgControl *ctrl = nullptr);
 // Nominal tile size (merge items per tile) used for L right-hand sides.
 int tile_items_for(int L);
 // Map key of the default plan for L (one-wave plans are keyed by minus their tile size: 512 is also
@@ -456,9 +462,38 @@ hipError_t launch_stream_read(const double *p, size_t bytes, int num_cus, hipStr
 std::string spmv_kernel_name(const mspmv_handle_s *h);
 std::string spmm_kernel_name(const mspmv_handle_s *h, const TilePlan &plan, int L);
 bool stream_nt(const mspmv_handle_s *h);
-bool supported_L(int L);
 
-// CG pieces
+// ---- runtime -> template dispatch ---------------------------------------------------
+// The native right-hand-side widths: every L-wide kernel is instantiated for exactly these.
+using NativeWidths = std::integer_sequence<int, 1, 2, 4, 8, 16>;
+template <typename F, int... N>
+inline hipError_t dispatch_width(int L, F &&f, std::integer_sequence<int, N...>)
+{
+    hipError_t e = hipErrorInvalidValue;
+    (void)((L == N && ((e = f(std::integral_constant<int, N>{})), true)) || ...);
+    return e;
+}
+// f(std::integral_constant<int, L>{}) for a native width L, returning f's hipError_t;
+// hipErrorInvalidValue for any other L.  f is a generic lambda:
+// `[&](auto Lc) { constexpr int LL = decltype(Lc)::value; ... }`; combinations a kernel does not
+// exist for are left out with `if constexpr` inside it.
+template <typename F>
+inline hipError_t dispatch_L(int L, F &&f)
+{
+    return dispatch_width(L, f, NativeWidths{});
+}
+inline bool supported_L(int L)
+{
+    return dispatch_L(L, [](auto) { return hipSuccess; }) == hipSuccess;
+}
+// f(std::true_type{}) or f(std::false_type{}): a runtime flag as a template argument.
+template <typename F>
+inline auto dispatch_bool(bool flag, F &&f)
+{
+    return flag ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// CG pieces (mspmv_cg_passes.hip, but for the stamped SpMV and the dot-mode tiles)
 hipError_t launch_cg_init(mspmv_handle_s *h, const double *d_b, double *d_x, int L, double tol, int nblk);
 // Diagnostic: the plain SpMV's k_spmv_tile in its stamped instantiation (hipErrorNotSupported for plans
 // that run another kernel); d_stamps [num_tiles][6] (mspmv_spmv_tile_stamps)
@@ -504,14 +539,14 @@ inline void consumer_level(int nslots, int stop, int L, long long *off, int *cou
     *count = c;
 }
 
-// Row-sharded CG (mspmv_dist.hip).  CgVecArgs lives in the kernels file; the dist code builds
-// it through this mirror.
-struct DistVecArgs {
-    long long n_elems;
+// Arguments of the CG's streaming vector passes (mspmv_cg_passes.hip): the single-GPU split, SPAI and
+// IC(0) iterations and the row-sharded CG (mspmv_dist.hip) fill one and launch the same kernels.
+struct CgVecArgs {
+    long long n_elems;       // n * L
     double *x;
     double *r;
-    const double *p;
-    double *p0;
+    const double *p;         // CG init: b.  update: p_new
+    double *p0;              // init: p0 = b
     const double *ap;
     CgScalars *scal;
     CgControl *ctrl;
@@ -520,17 +555,39 @@ struct DistVecArgs {
     double *hist;
     int hist_cap;
     double tol;
+    // Row-sharded CG (mspmv_dist.hip): red_in = all-reduced p.Ap per column (alpha is formed
+    // from it in every block); red_out = where the last block leaves this rank's partial sums
+    // (b.b at init, r.r at update) for the all-reduce, instead of finishing the scalars.
     const double *red_in;
     double *red_out;
-    unsigned *gtickets;
-    int pcg;
-    int lazy_x;  // (single-GPU split CG only: 0 here)
+    unsigned *gtickets;  // reduce_slots tickets
+    int pcg;             // k_cg_update: SPAI-PCG (beta and rs_old come from R.Z, k_fold_dot)
+    // Single-GPU split CG: x += alpha p is deferred from the update to the next p update (which
+    // reads p anyway before overwriting it), so the update neither reads p nor reads / writes x.
+    // k_cg_update stores each column's masked alpha in scal[j].alpha and raises ctrl->x_pending;
+    // k_dist_pupdate applies the term; the fold after it clears the flag; k_cg_xflush applies the
+    // term still pending when the solve ends.  Same expression x + alpha p: bit-identical x.
+    int lazy_x;
+    // Streaming passes of the split CG sweep their chunks of gridDim x kBlock elements last to
+    // first (rev = 1) or first to last, alternately, so a pass starts on the lines the previous
+    // pass touched last -- still in the 256 MiB Infinity Cache (every lane keeps its column pair).
     int rev;
+    // Cache policy of the split CG's passes (the 256 MiB Infinity Cache holds about one L = 8 vector
+    // of the nlpkkt120 size): a vector read for the last time before another pass streams over it is
+    // loaded nontemporal -- Ap in the r update, p in the p.Ap pass (next read by the p update, two
+    // passes on), r and x in the p update (x is touched once per iteration: stored nontemporal too) --
+    // so the lines the NEXT pass starts on stay cached: 0.855 -> 0.793 ms per iteration (r04al-r04an;
+    // r loaded nontemporal in the r update measured even).
 };
-// which: 0 init partial sums (b.b -> red_out), 1 init finish (red_in = all-reduced b.b),
-// 2 p update, 3 x/r update (alpha from red_in = all-reduced p.Ap; r.r -> red_out),
-// 4 finish (red_in = p.Ap, red_out = all-reduced r.r)
-hipError_t launch_dist_vec_mirror(int which, const DistVecArgs &a, int L, int nblk, double *p, hipStream_t s);
+// The vector passes launch_dist_vec runs on a CgVecArgs.
+enum class CgVecPass {
+    InitPartials,  // k_cg_init: x = 0, r = p0 = b, b.b partial sums -> red_out
+    InitFinish,    // k_dist_init_finish: scalars from red_in = all-reduced b.b
+    PUpdate,       // k_dist_pupdate: p = r + beta p (p: the `p` argument)
+    XrUpdate,      // k_cg_update: x, r (alpha from red_in = all-reduced p.Ap when set; r.r -> red_out)
+    Finish,        // k_dist_finish: stop test, beta (red_in = p.Ap, red_out = all-reduced r.r)
+};
+hipError_t launch_dist_vec(CgVecPass pass, const CgVecArgs &a, int L, int nblk, double *p, hipStream_t s);
 hipError_t launch_dist_pack(const double *p, const int *idx, long long n_elems, int L, double *send,
                             const CgControl *ctrl, hipStream_t s);
 hipError_t launch_spmm_dot(mspmv_handle_s *h, const TilePlan &plan, const double *d_X, double *d_Y, int L,

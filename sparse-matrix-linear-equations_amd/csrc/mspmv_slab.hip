@@ -560,25 +560,21 @@ hipError_t launch_slab(mspmv_handle_s *h, const TilePlan &plan, const double *d_
     const dim3 grid(plan.num_tiles);
     if (s.cfg == 2) {
         const dim3 tb(kSlabCfgs[2].threads);
-        if (nt && s.pack)
-            hipLaunchKernelGGL((k_spmv_sell<true, true>), grid, tb, 0, h->stream, a);
-        else if (nt)
-            hipLaunchKernelGGL((k_spmv_sell<true, false>), grid, tb, 0, h->stream, a);
-        else if (s.pack)
-            hipLaunchKernelGGL((k_spmv_sell<false, true>), grid, tb, 0, h->stream, a);
-        else
-            hipLaunchKernelGGL((k_spmv_sell<false, false>), grid, tb, 0, h->stream, a);
+        dispatch_bool(nt, [&](auto ntc) {
+            dispatch_bool(s.pack, [&](auto pack) {
+                hipLaunchKernelGGL((k_spmv_sell<decltype(ntc)::value, decltype(pack)::value>), grid, tb, 0, h->stream, a);
+            });
+        });
         return hipGetLastError();
     }
     const dim3 b1(kSlabCfgs[1].threads), b0(kSlabCfgs[0].threads);
-    if (s.cfg == 1 && nt)
-        hipLaunchKernelGGL((k_spmv_slab<true, 1>), grid, b1, 0, h->stream, a);
-    else if (s.cfg == 1)
-        hipLaunchKernelGGL((k_spmv_slab<false, 1>), grid, b1, 0, h->stream, a);
-    else if (nt)
-        hipLaunchKernelGGL((k_spmv_slab<true, 0>), grid, b0, 0, h->stream, a);
-    else
-        hipLaunchKernelGGL((k_spmv_slab<false, 0>), grid, b0, 0, h->stream, a);
+    dispatch_bool(nt, [&](auto ntc) {
+        constexpr bool NT = decltype(ntc)::value;
+        if (s.cfg == 1)
+            hipLaunchKernelGGL((k_spmv_slab<NT, 1>), grid, b1, 0, h->stream, a);
+        else
+            hipLaunchKernelGGL((k_spmv_slab<NT, 0>), grid, b0, 0, h->stream, a);
+    });
     return hipGetLastError();
 }
 
@@ -1597,10 +1593,9 @@ template <int CFG>
 static void launch_slab_mm_cfg(const SlabMmArgs &a, bool nt, hipStream_t s)
 {
     const dim3 grid(a.num_tiles), block(kSlabMmCfgs[CFG].threads);
-    if (nt)
-        hipLaunchKernelGGL((k_spmm_slab<CFG, true>), grid, block, 0, s, a);
-    else
-        hipLaunchKernelGGL((k_spmm_slab<CFG, false>), grid, block, 0, s, a);
+    dispatch_bool(nt, [&](auto ntc) {
+        hipLaunchKernelGGL((k_spmm_slab<CFG, decltype(ntc)::value>), grid, block, 0, s, a);
+    });
 }
 
 hipError_t launch_slab_mm(mspmv_handle_s *h, const TilePlan &plan, const double *d_X, double *d_Y, int L, int ld,

@@ -70,7 +70,7 @@ def _check(tmp_path, orc, world, L):
     assert np.linalg.norm(Xg - Xo) <= 1e-8 * np.linalg.norm(Xo)
 
 
-@pytest.mark.parametrize("L", [1, 8])
+@pytest.mark.parametrize("L", [1, 8, 16])
 def test_dist_world1(tmp_path, orc, L):
     import mspmv
     _run_rank(0, 1, mspmv.comm_unique_id(), L, str(tmp_path))

@@ -1,5 +1,6 @@
 #!/bin/bash
-# VGPR / SGPR / spill / LDS of the kernels in an in-tree HIP object (default: mspmv_kernels.o).
+# VGPR / SGPR / spill / LDS of the kernels in an in-tree HIP object (default: mspmv_kernels.o, the
+# product kernels; the CG passes are in mspmv_cg_passes.o).
 #   usage: tools/regs.sh [object.o] [name-substring ...]
 set -eu
 B=/opt/rocm/lib/llvm/bin
