@@ -166,6 +166,29 @@ MSPMV_API mspmv_status mspmv_dcg_multi_dev(mspmv_handle h, const double *d_B, do
                                  double tolerance, mspmv_spmm_kernel kernel, int *iters, double *max_err_hist,
                                  int hist_cap);
 
+/* ---- BiCGSTAB (nonsymmetric systems) -------------------------------------------------- */
+/* Multi-RHS BiCGSTAB for a square matrix that need not be symmetric or definite (van der
+ * Vorst's recurrence, unpreconditioned, shadow residual rhat = b); only A X is needed, no
+ * transpose.  No reference counterpart (every solver of the reference is a CG).  Per column j of
+ * the interleaved n x L panels: X = 0, R = P = B, rho = B.B; per iteration V = A P,
+ * alpha = rho / (rhat.V), s = R - alpha V, X += alpha P, T = A s, omega = T.s / T.T (T.T == 0:
+ * s is exactly 0 and omega = 0, not a breakdown), X += omega s, R = s - omega T, stop test on
+ * sqrt(R.R)/||B_j|| < tolerance with per-column converged masks (alpha = omega = beta = 0 once
+ * converged; ||B_j|| == 0 -> 1), rho' = rhat.R, beta = (rho'/rho)(alpha/omega), rho = rho',
+ * P = R + beta (P - omega V).  Returns the iteration count in *iters (max_iters when not every
+ * column converged); max_err_hist (optional, capacity hist_cap) receives the per-iteration max
+ * over the columns of sqrt(R.R)/||B_j||.  Breakdown is per column, by mspmv_dcg_multi's rule: a
+ * non-finite alpha, omega or beta (a zero RHS column; rho = 0 or omega = 0 on a column still
+ * iterating) freezes the column at its last finite iterate and leaves it out of the history, the
+ * other columns keep iterating, and the call returns MSPMV_ERR_BREAKDOWN with X holding every
+ * column's result.  Any L >= 1 (column groups as mspmv_dcg_multi).  MSPMV_ERR_INVALID for a
+ * non-square matrix, max_iters < 0, null vectors, or device vectors not 16-byte aligned. */
+MSPMV_API mspmv_status mspmv_dbicgstab_multi(mspmv_handle h, const double *B, double *X, int L, int max_iters,
+                                             double tolerance, int *iters, double *max_err_hist, int hist_cap);
+MSPMV_API mspmv_status mspmv_dbicgstab_multi_dev(mspmv_handle h, const double *d_B, double *d_X, int L,
+                                                 int max_iters, double tolerance, int *iters, double *max_err_hist,
+                                                 int hist_cap);
+
 /* ---- SPAI-preconditioned block CG ---------------------------------------------------- */
 /* SPAI preconditioner M with A's own pattern, SparseApproximateInversion
  * (work_2025/cg/sparse_approximate_inversion.hpp:40-321): column k of M minimises

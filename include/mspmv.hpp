@@ -300,6 +300,22 @@ int CGSolveMultiple(Csr &a, const ValueT *B, ValueT *X, int num_vectors, int max
     return iters;
 }
 
+// Multi-RHS BiCGSTAB for a square matrix that need not be symmetric (mspmv_dbicgstab_multi), in
+// CGSolveMultiple's calling form.  No reference counterpart: every solver of the reference is a CG.
+template <typename Csr, typename ValueT>
+int BiCGStabSolveMultiple(Csr &a, const ValueT *B, ValueT *X, int num_vectors, int max_iters, ValueT tolerance,
+                          std::vector<double> *max_errors = nullptr)
+{
+    int iters = 0;
+    std::vector<double> hist(max_errors ? (size_t)std::max(max_iters, 0) : 0);
+    detail::note_cg(mspmv_dbicgstab_multi(detail::handle_for(a), B, X, num_vectors, max_iters, tolerance, &iters,
+                                          max_errors ? hist.data() : nullptr, max_errors ? max_iters : 0),
+                    "BiCGStabSolveMultiple");
+    if (max_errors)
+        max_errors->assign(hist.begin(), hist.begin() + std::min<size_t>(hist.size(), (size_t)iters));
+    return iters;
+}
+
 // work_2025/cg/incomplete_cholesky_decomp.hpp:11-78 (host: setup, as in the reference)
 template <typename Csr>
 void TransposeCsr(const Csr &in, Csr &out)
@@ -617,6 +633,13 @@ int CGSolveMultiple(CsrMatrix<ValueT, OffsetT> &a, const ValueT *B, ValueT *X, i
                     ValueT tolerance, SpmmKernel kernel_type, std::vector<double> *max_errors = nullptr)
 {
     return mspmv_ref::CGSolveMultiple(a, B, X, num_vectors, max_iters, tolerance, kernel_type, max_errors);
+}
+// (no reference counterpart) multi-RHS BiCGSTAB for nonsymmetric systems
+template <typename ValueT, typename OffsetT>
+int BiCGStabSolveMultiple(CsrMatrix<ValueT, OffsetT> &a, const ValueT *B, ValueT *X, int num_vectors, int max_iters,
+                          ValueT tolerance, std::vector<double> *max_errors = nullptr)
+{
+    return mspmv_ref::BiCGStabSolveMultiple(a, B, X, num_vectors, max_iters, tolerance, max_errors);
 }
 template <typename ValueT, typename OffsetT>
 void TestCGMultipleRHS(CsrMatrix<ValueT, OffsetT> &a, ValueT *b_vectors, ValueT *x_solutions, int max_iters,

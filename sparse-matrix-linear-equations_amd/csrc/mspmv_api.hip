@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -1115,6 +1116,7 @@ mspmv_status mspmv_destroy(mspmv_handle h)
     dev_free(h->d_p0);
     dev_free(h->d_p1);
     dev_free(h->d_ap);
+    dev_free(h->d_rhat);
     dev_free(h->d_partials);
     dev_free(h->d_partials_b);
     dev_free(h->d_gtickets);
@@ -1128,6 +1130,10 @@ mspmv_status mspmv_destroy(mspmv_handle h)
         (void)hipGraphExecDestroy(h->cg_exec);
     if (h->cg_graph)
         (void)hipGraphDestroy(h->cg_graph);
+    if (h->bicg_exec)
+        (void)hipGraphExecDestroy(h->bicg_exec);
+    if (h->bicg_graph)
+        (void)hipGraphDestroy(h->bicg_graph);
     if (h->d_flush)
         (void)hipFree(h->d_flush);
     if (h->h_ctrl)
@@ -1213,9 +1219,16 @@ mspmv_status mspmv_set_cu_limit(mspmv_handle h, int num_cus)
         (void)hipGraphExecDestroy(h->cg_exec);
     if (h->cg_graph)
         (void)hipGraphDestroy(h->cg_graph);
+    if (h->bicg_exec)
+        (void)hipGraphExecDestroy(h->bicg_exec);
+    if (h->bicg_graph)
+        (void)hipGraphDestroy(h->bicg_graph);
     h->cg_exec = nullptr;
     h->cg_graph = nullptr;
     h->cg_graph_key.clear();
+    h->bicg_exec = nullptr;
+    h->bicg_graph = nullptr;
+    h->bicg_graph_key.clear();
     if (h->own_stream)
         (void)hipStreamDestroy(h->stream);
     h->stream = s;
@@ -1451,7 +1464,9 @@ mspmv_status mspmv_test_poison_tickets(mspmv_handle h, unsigned value, int flags
 }
 
 // ---- CG ------------------------------------------------------------------------------------
-static mspmv_status ensure_cg_workspace(mspmv_handle_s *h, int L, int nblk, int num_tiles, int hist_cap)
+// fold_width: columns of a partial row when wider than L (BiCGSTAB's two-dot folds: 2 L)
+static mspmv_status ensure_cg_workspace(mspmv_handle_s *h, int L, int nblk, int num_tiles, int hist_cap,
+                                        int fold_width = 0)
 {
     // L = 1: the pipelined CG's p buffers hold {r, p} interleaved (2 m doubles each)
     const size_t elems = (size_t)h->m * std::max(L, 2);
@@ -1468,7 +1483,7 @@ static mspmv_status ensure_cg_workspace(mspmv_handle_s *h, int L, int nblk, int 
         h->cg_cap_elems = elems;
     }
     const size_t slots = (size_t)std::max(nblk, num_tiles);
-    const size_t pcap = partials_capacity(slots, L);
+    const size_t pcap = partials_capacity(slots, std::max(L, fold_width));
     if (pcap > h->partials_cap) {
         dev_free(h->d_partials);
         h->partials_cap = 0;
@@ -1562,6 +1577,170 @@ static mspmv_status resident_for(mspmv_handle_s *h, ResidentCg **out)
     return MSPMV_OK;
 }
 
+// ---- the protocol every batched solve on a handle follows (cg_solve_native, bicgstab_solve_native) ----
+// Prologue, on the handle's stream, before the solver's init: a zeroed control word, zeroed fold tickets and
+// split-row tickets of the plans the solve multiplies with, and the pending mspmv_test_poison_tickets flags
+// (returned in *poison_out; consumed).
+static mspmv_status solve_prologue(mspmv_handle_s *h, std::initializer_list<const TilePlan *> plans, int *poison_out)
+{
+    HIP_TRY(hipMemsetAsync(h->d_ctrl, 0, sizeof(CgControl), h->stream));
+    // test hook (mspmv_test_poison_tickets): dirty fold tickets at the first fold, as an unordered zeroing
+    // of freshly allocated (recycled) memory leaves them
+    const int poison = h->poison_flags;
+    h->poison_flags = 0;
+    *poison_out = poison;
+    // the fold tickets reset themselves, but a solve that stopped early or faulted may leave some
+    // raised: every solve starts from zeroed ones (a few KB, on the solve's stream)
+    HIP_TRY(hipMemsetAsync(h->d_gtickets, 0, sizeof(unsigned) * h->gtickets_cap, h->stream));
+    if (poison & MSPMV_POISON_NO_STOP)
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)&h->d_ctrl->fault_no_stop, 1, 1, h->stream));
+    // Split-row tickets reset themselves when every tile sharing a row reaches close_split_rows; a CG
+    // SpMM returns at its stop test before that (all tiles alike, but an aborted launch might not), so
+    // every solve starts from zeroed tickets (ADVICE r04)
+    for (const TilePlan *tp : plans)
+        if (tp && tp->d_fix_cnt)
+            HIP_TRY(hipMemsetAsync(tp->d_fix_cnt, 0, sizeof(unsigned) * (size_t)tp->num_tiles, h->stream));
+    return MSPMV_OK;
+}
+
+// test hook, after the solver's init: the iterations' folds meet dirty tickets
+static mspmv_status solve_poison_fill(mspmv_handle_s *h, int poison)
+{
+    if (poison & MSPMV_POISON_FILL)
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)h->d_gtickets, (int)h->poison_value, h->gtickets_cap, h->stream));
+    return MSPMV_OK;
+}
+
+// A solver's cached iteration graph on the handle: K iterations captured from the handle's stream, reused
+// while everything it was captured with (the key) is unchanged (instantiation costs ms).
+struct SolverGraph {
+    hipGraph_t &graph;
+    hipGraphExec_t &exec;
+    std::vector<const void *> &key;
+};
+using IterateFn = std::function<hipError_t(int)>;  // enqueue iteration i of a batch on the handle's stream
+static mspmv_status solver_graph(mspmv_handle_s *h, SolverGraph g, const std::vector<const void *> &key, int K,
+                                 const IterateFn &iterate, const char *name)
+{
+    if (g.exec && g.key == key)
+        return MSPMV_OK;
+    if (g.exec)
+        (void)hipGraphExecDestroy(g.exec);
+    if (g.graph)
+        (void)hipGraphDestroy(g.graph);
+    g.exec = nullptr;
+    g.graph = nullptr;
+    g.key.clear();
+    hipError_t e = hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal);
+    for (int i = 0; i < K && e == hipSuccess; ++i)
+        e = iterate(i);
+    hipGraph_t graph = nullptr;
+    hipError_t e2 = hipStreamEndCapture(h->stream, &graph);
+    if (e == hipSuccess)
+        e = e2;
+    g.graph = graph;
+    if (e == hipSuccess)
+        e = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
+    if (e != hipSuccess) {
+        set_error(std::string(name) + " graph capture: " + hipGetErrorString(e));
+        return MSPMV_ERR_HIP;
+    }
+    g.key = key;
+    return MSPMV_OK;
+}
+
+// The iterations, in batches of K (a replay of exec when given and the batch is whole, else launched one by
+// one), the control word copied back after each.  Pipelined: batch b+1 is queued before batch b's control
+// word is inspected, so the GPU never idles on the host check; after convergence at most one batch of
+// kernels runs, each returning at its first instruction (the `done` test).
+static mspmv_status solve_batches(mspmv_handle_s *h, int K, int max_iters, hipGraphExec_t exec, int poison,
+                                  hipEvent_t (&evs)[2], const char *name, const IterateFn &iterate)
+{
+    if (hipEventCreateWithFlags(&evs[0], hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&evs[1], hipEventDisableTiming) != hipSuccess) {
+        set_error("hipEventCreate failed");
+        return MSPMV_ERR_HIP;
+    }
+    int iterations_enqueued = 0;
+    auto iterate_hook = [&](int i) -> hipError_t {
+        hipError_t e = iterate(i);
+        if (e == hipSuccess && (poison & MSPMV_POISON_LATE_ZERO) && ++iterations_enqueued == 1)
+            e = hipMemsetAsync(h->d_gtickets, 0, sizeof(unsigned) * h->gtickets_cap, h->stream);  // the late zeroing
+        return e;
+    };
+    int launched = 0, pending = 0, oldest = 0, slot = 0;
+    for (;;) {
+        const int k = std::min(K, max_iters - launched);
+        if (k > 0) {
+            hipError_t e = hipSuccess;
+            if (k == K && exec)
+                e = hipGraphLaunch(exec, h->stream);
+            else
+                for (int i = 0; i < k && e == hipSuccess; ++i)
+                    e = iterate_hook(i);
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(&h->h_ctrl[slot], h->d_ctrl, sizeof(CgControl), hipMemcpyDeviceToHost, h->stream);
+            if (e == hipSuccess)
+                e = hipEventRecord(evs[slot], h->stream);
+            if (e != hipSuccess) {
+                set_error(std::string(name) + " launch: " + hipGetErrorString(e));
+                return MSPMV_ERR_HIP;
+            }
+            launched += k;
+            ++pending;
+            slot ^= 1;
+        }
+        if (pending == 0)
+            break;
+        if (pending == 2 || k <= 0) {
+            if (hipEventSynchronize(evs[oldest]) != hipSuccess) {
+                set_error(std::string(name) + " event sync failed");
+                return MSPMV_ERR_HIP;
+            }
+            --pending;
+            const bool done = h->h_ctrl[oldest].done != 0;
+            oldest ^= 1;
+            if (done)
+                break;
+        }
+    }
+    return MSPMV_OK;
+}
+
+// After the last launch: wait, read the control word into *fin, hand out the iteration count and the history,
+// and report a ticket fault.  st: the solve's status so far (an error is passed through after the wait).
+static mspmv_status solve_collect(mspmv_handle_s *h, mspmv_status st, hipEvent_t (&evs)[2], int saved_cap, int use_cap,
+                                  int *iters, double *hist, CgControl *fin, const char *name)
+{
+    hipError_t e = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess)
+        e = hipMemcpy(fin, h->d_ctrl, sizeof(CgControl), hipMemcpyDeviceToHost);
+    if (st == MSPMV_OK && e != hipSuccess) {
+        set_error(std::string(name) + " finish: " + hipGetErrorString(e));
+        st = MSPMV_ERR_HIP;
+    }
+    for (auto &ev : evs)
+        if (ev)
+            (void)hipEventDestroy(ev);
+    h->hist_cap = saved_cap;
+    if (st != MSPMV_OK)
+        return st;
+    const int it = fin->done ? fin->iters_out : fin->iter;
+    if (iters)
+        *iters = it;
+    if (hist && use_cap > 0) {
+        const int nh = std::min(it, use_cap);
+        if (nh > 0)
+            HIP_TRY(hipMemcpy(hist, h->d_hist, sizeof(double) * nh, hipMemcpyDeviceToHost));
+    }
+    if (fin->fault) {
+        set_error(std::string(name) + ": a reduction ticket drew past its group (the ticket array was not zero when a "
+                  "fold began): the solve stopped, X is not a solution");
+        return MSPMV_ERR_FAULT;
+    }
+    return MSPMV_OK;
+}
+
 // CG; SPAI-preconditioned CG with the preconditioner's handle hm; or IC(0)-preconditioned CG
 // with the factor ic.
 static mspmv_status cg_solve_native(mspmv_handle_s *h, const double *d_b, double *d_x, int L, int max_iters,
@@ -1647,22 +1826,8 @@ static mspmv_status cg_solve_native(mspmv_handle_s *h, const double *d_b, double
                                   : "split (p update, SpMM, p.Ap, update)";
     const int saved_cap = h->hist_cap;
     h->hist_cap = use_cap;  // kernels record only what the caller asked for
-    HIP_TRY(hipMemsetAsync(h->d_ctrl, 0, sizeof(CgControl), h->stream));
-    // test hook (mspmv_test_poison_tickets): dirty fold tickets at the first fold, as an unordered zeroing
-    // of freshly allocated (recycled) memory leaves them
-    const int poison = h->poison_flags;
-    h->poison_flags = 0;
-    // the fold tickets reset themselves, but a solve that stopped early or faulted may leave some
-    // raised: every solve starts from zeroed ones (a few KB, on the solve's stream)
-    HIP_TRY(hipMemsetAsync(h->d_gtickets, 0, sizeof(unsigned) * h->gtickets_cap, h->stream));
-    if (poison & MSPMV_POISON_NO_STOP)
-        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)&h->d_ctrl->fault_no_stop, 1, 1, h->stream));
-    // Split-row tickets reset themselves when every tile sharing a row reaches close_split_rows; a CG
-    // SpMM returns at its stop test before that (all tiles alike, but an aborted launch might not), so
-    // every solve starts from zeroed tickets (ADVICE r04)
-    for (const TilePlan *tp : {plan, splan, mplan})
-        if (tp && tp->d_fix_cnt)
-            HIP_TRY(hipMemsetAsync(tp->d_fix_cnt, 0, sizeof(unsigned) * (size_t)tp->num_tiles, h->stream));
+    int poison = 0;
+    ST_TRY(solve_prologue(h, {plan, splan, mplan}, &poison));
     if (hm)
         HIP_TRY(launch_pcg_init(h, hm, *mplan, d_b, d_x, L, tol, nblk));
     else if (ic)
@@ -1671,21 +1836,13 @@ static mspmv_status cg_solve_native(mspmv_handle_s *h, const double *d_b, double
         HIP_TRY(launch_cg1_init(h, d_b, d_x, nblk));
     else
         HIP_TRY(launch_cg_init(h, d_b, d_x, L, tol, nblk));
-    if (poison & MSPMV_POISON_FILL)  // test hook: the iterations' folds meet dirty tickets (after the init's)
-        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)h->d_gtickets, (int)h->poison_value, h->gtickets_cap, h->stream));
+    ST_TRY(solve_poison_fill(h, poison));  // (after the init's fold)
     auto iterate = [&](int i) -> hipError_t {
         if (hm)
             return launch_pcg_iteration(h, hm, *plan, *mplan, d_x, L, nblk, tol);
         if (ic)
             return launch_pcg_ic0_iteration(h, ic, *plan, d_x, L, nblk, tol);
         return launch_cg_iteration(h, *plan, splan, dot_fused, d_x, L, i & 1, nblk, tol);
-    };
-    int iterations_enqueued = 0;
-    auto iterate_hook = [&](int i) -> hipError_t {
-        hipError_t e = iterate(i);
-        if (e == hipSuccess && (poison & MSPMV_POISON_LATE_ZERO) && ++iterations_enqueued == 1)
-            e = hipMemsetAsync(h->d_gtickets, 0, sizeof(unsigned) * h->gtickets_cap, h->stream);  // the late zeroing
-        return e;
     };
 
     const int K = cg_batch_iters(h->m, h->nnz, L);  // iterations per graph replay (even: p buffers alternate)
@@ -1707,80 +1864,12 @@ static mspmv_status cg_solve_native(mspmv_handle_s *h, const double *d_b, double
             reinterpret_cast<const void *>((uintptr_t)(hm ? hm->gen : 0)),
             reinterpret_cast<const void *>((uintptr_t)(ic ? ic->gen : 0)),
             reinterpret_cast<const void *>((intptr_t)K), reinterpret_cast<const void *>((intptr_t)dot_fused)};
-        if (!h->cg_exec || h->cg_graph_key != key) {
-            if (h->cg_exec)
-                (void)hipGraphExecDestroy(h->cg_exec);
-            if (h->cg_graph)
-                (void)hipGraphDestroy(h->cg_graph);
-            h->cg_exec = nullptr;
-            h->cg_graph = nullptr;
-            h->cg_graph_key.clear();
-            hipError_t e = hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal);
-            for (int i = 0; i < K && e == hipSuccess; ++i)
-                e = iterate(i);
-            hipGraph_t graph = nullptr;
-            hipError_t e2 = hipStreamEndCapture(h->stream, &graph);
-            if (e == hipSuccess)
-                e = e2;
-            h->cg_graph = graph;
-            if (e == hipSuccess)
-                e = hipGraphInstantiate(&h->cg_exec, graph, nullptr, nullptr, 0);
-            if (e != hipSuccess) {
-                set_error(std::string("CG graph capture: ") + hipGetErrorString(e));
-                st = MSPMV_ERR_HIP;
-            } else {
-                h->cg_graph_key = key;
-            }
-        }
+        st = solver_graph(h, SolverGraph{h->cg_graph, h->cg_exec, h->cg_graph_key}, key, K, iterate, "CG");
         exec = h->cg_exec;
     }
     hipEvent_t evs[2] = {nullptr, nullptr};
-    if (st == MSPMV_OK && (hipEventCreateWithFlags(&evs[0], hipEventDisableTiming) != hipSuccess ||
-                           hipEventCreateWithFlags(&evs[1], hipEventDisableTiming) != hipSuccess)) {
-        set_error("hipEventCreate failed");
-        st = MSPMV_ERR_HIP;
-    }
-    // Pipelined: batch b+1 is queued before batch b's control word is inspected, so the GPU
-    // never idles on the host check; after convergence at most one batch of kernels runs,
-    // each returning at its first instruction (the `done` test).
-    int launched = 0, pending = 0, oldest = 0, slot = 0;
-    while (st == MSPMV_OK) {
-        const int k = std::min(K, max_iters - launched);
-        if (k > 0) {
-            hipError_t e = hipSuccess;
-            if (k == K && exec)
-                e = hipGraphLaunch(exec, h->stream);
-            else
-                for (int i = 0; i < k && e == hipSuccess; ++i)
-                    e = iterate_hook(i);
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(&h->h_ctrl[slot], h->d_ctrl, sizeof(CgControl), hipMemcpyDeviceToHost, h->stream);
-            if (e == hipSuccess)
-                e = hipEventRecord(evs[slot], h->stream);
-            if (e != hipSuccess) {
-                set_error(std::string("CG launch: ") + hipGetErrorString(e));
-                st = MSPMV_ERR_HIP;
-                break;
-            }
-            launched += k;
-            ++pending;
-            slot ^= 1;
-        }
-        if (pending == 0)
-            break;
-        if (pending == 2 || k <= 0) {
-            if (hipEventSynchronize(evs[oldest]) != hipSuccess) {
-                set_error("CG event sync failed");
-                st = MSPMV_ERR_HIP;
-                break;
-            }
-            --pending;
-            const bool done = h->h_ctrl[oldest].done != 0;
-            oldest ^= 1;
-            if (done)
-                break;
-        }
-    }
+    if (st == MSPMV_OK)
+        st = solve_batches(h, K, max_iters, exec, poison, evs, "CG", iterate);
     if (st == MSPMV_OK && max_iters > 0 && !hm && !ic) {
         // pipelined: the last iteration's stop test (a no-op once the solve has stopped); both
         // forms: the deferred x += alpha p of the last update
@@ -1790,33 +1879,9 @@ static mspmv_status cg_solve_native(mspmv_handle_s *h, const double *d_b, double
             st = MSPMV_ERR_HIP;
         }
     }
-    hipError_t e = hipStreamSynchronize(h->stream);
     CgControl fin{};
-    if (e == hipSuccess)
-        e = hipMemcpy(&fin, h->d_ctrl, sizeof(CgControl), hipMemcpyDeviceToHost);
-    if (st == MSPMV_OK && e != hipSuccess) {
-        set_error(std::string("CG finish: ") + hipGetErrorString(e));
-        st = MSPMV_ERR_HIP;
-    }
-    for (auto &ev : evs)
-        if (ev)
-            (void)hipEventDestroy(ev);
-    h->hist_cap = saved_cap;
-    if (st != MSPMV_OK)
-        return st;
+    ST_TRY(solve_collect(h, st, evs, saved_cap, use_cap, iters, hist, &fin, "CG"));
     const int it = fin.done ? fin.iters_out : fin.iter;
-    if (iters)
-        *iters = it;
-    if (hist && use_cap > 0) {
-        const int nh = std::min(it, use_cap);
-        if (nh > 0)
-            HIP_TRY(hipMemcpy(hist, h->d_hist, sizeof(double) * nh, hipMemcpyDeviceToHost));
-    }
-    if (fin.fault) {
-        set_error("CG: a reduction ticket drew past its group (the ticket array was not zero when a fold began): "
-                  "the solve stopped, X is not a solution");
-        return MSPMV_ERR_FAULT;
-    }
     if (fin.breakdown == 2) {
         if (iters)
             *iters = fin.iter;
@@ -1838,14 +1903,17 @@ static mspmv_status cg_solve_native(mspmv_handle_s *h, const double *d_b, double
 // column groups of native widths, each copied into a contiguous panel and back.  The iteration
 // count is the groups' maximum; the history is the max over groups, a finished group's columns
 // frozen at their last residual (alpha = 0 leaves r unchanged), as the reference records them.
-static mspmv_status cg_solve_dev(mspmv_handle_s *h, const double *d_b, double *d_x, int L, int max_iters,
-                                 double tol, int *iters, double *hist, int hist_cap, mspmv_handle_s *hm = nullptr,
-                                 mspmv_ic0_s *ic = nullptr)
+// native(d_b, d_x, width, iters, hist, hist_cap): the solver on a panel of native width (cg_solve_native,
+// bicgstab_solve_native); name / broke_msg: the solver's name and its breakdown report in the error text.
+using NativeSolveFn = std::function<mspmv_status(const double *, double *, int, int *, double *, int)>;
+static mspmv_status solve_dev_groups(mspmv_handle_s *h, const double *d_b, double *d_x, int L, int *iters,
+                                     double *hist, int hist_cap, const NativeSolveFn &native, const char *name,
+                                     const char *broke_msg)
 {
     if (L < 1)
         return invalid("L must be >= 1");
     if (supported_L(L) || h->m == 0)
-        return cg_solve_native(h, d_b, d_x, supported_L(L) ? L : 1, max_iters, tol, iters, hist, hist_cap, hm, ic);
+        return native(d_b, d_x, supported_L(L) ? L : 1, iters, hist, hist_cap);
     if (!d_b || !d_x)
         return invalid("null vector");
     const size_t m = (size_t)h->m;
@@ -1868,7 +1936,7 @@ static mspmv_status cg_solve_dev(mspmv_handle_s *h, const double *d_b, double *d
         }
         std::vector<double> hg((size_t)cap);
         int it = 0;
-        st = cg_solve_native(h, gb, gx, w, max_iters, tol, &it, cap ? hg.data() : nullptr, cap, hm, ic);
+        st = native(gb, gx, w, &it, cap ? hg.data() : nullptr, cap);
         if (st == MSPMV_ERR_BREAKDOWN) {
             broke = true;
             st = MSPMV_OK;
@@ -1893,11 +1961,11 @@ static mspmv_status cg_solve_dev(mspmv_handle_s *h, const double *d_b, double *d
     dev_free(gb);
     dev_free(gx);
     if (st == MSPMV_OK && faulted) {
-        set_error("CG: a reduction ticket drew past its group in at least one column group: X is not a solution");
+        set_error(std::string(name) +
+                  ": a reduction ticket drew past its group in at least one column group: X is not a solution");
         st = MSPMV_ERR_FAULT;
     } else if (st == MSPMV_OK && broke) {
-        set_error("CG breakdown: p.Ap gave a non-finite alpha in at least one column (frozen; the other "
-                  "columns were solved)");
+        set_error(broke_msg);
         st = MSPMV_ERR_BREAKDOWN;
     }
     if (iters)
@@ -1912,9 +1980,111 @@ static mspmv_status cg_solve_dev(mspmv_handle_s *h, const double *d_b, double *d
     return st;
 }
 
-static mspmv_status cg_solve_host(mspmv_handle h, const double *B, double *X, int L, int max_iters, double tol,
-                                  int *iters, double *hist, int hist_cap, mspmv_handle hm = nullptr,
-                                  mspmv_ic0 ic = nullptr)
+static mspmv_status cg_solve_dev(mspmv_handle_s *h, const double *d_b, double *d_x, int L, int max_iters,
+                                 double tol, int *iters, double *hist, int hist_cap, mspmv_handle_s *hm = nullptr,
+                                 mspmv_ic0_s *ic = nullptr)
+{
+    return solve_dev_groups(
+        h, d_b, d_x, L, iters, hist, hist_cap,
+        [&](const double *b, double *x, int w, int *it, double *hg, int cap) {
+            return cg_solve_native(h, b, x, w, max_iters, tol, it, hg, cap, hm, ic);
+        },
+        "CG",
+        "CG breakdown: p.Ap gave a non-finite alpha in at least one column (frozen; the other columns were solved)");
+}
+
+// BiCGSTAB on a panel of native width (mspmv_bicgstab.hip), by cg_solve_native's protocol: control word and
+// tickets zeroed on the handle's stream before the init, iterations in batches of cg_batch_iters with the
+// control word copied back per batch, a batch replayed as a graph captured from the handle's one stream (a
+// linear chain) and cached under the solver's own exec and key; fewer than a batch of iterations run ungraphed.
+static mspmv_status bicgstab_solve_native(mspmv_handle_s *h, const double *d_b, double *d_x, int L, int max_iters,
+                                          double tol, int *iters, double *hist, int hist_cap)
+{
+    if (h->m != h->n)
+        return invalid("BiCGSTAB needs a square matrix");
+    if (!supported_L(L))
+        return (set_error("L must be one of 1, 2, 4, 8, 16"), MSPMV_ERR_UNSUPPORTED);
+    if (max_iters < 0)
+        return invalid("max_iters < 0");
+    if (h->m > 0 && (!d_b || !d_x))
+        return invalid("null vector");
+    if (!aligned16(d_b) || !aligned16(d_x))
+        return invalid("BiCGSTAB vectors must be 16-byte aligned");
+    if (iters)
+        *iters = 0;
+    if (h->m == 0)
+        return MSPMV_OK;
+    // the two products run on the plan the handle's plain L-wide product takes (offset windows, column slabs),
+    // else on the merge tiles: decided here, before any graph capture (it may copy the matrix to the host)
+    const TilePlan *plan = nullptr, *splan = nullptr;
+    ST_TRY(get_plan(h, L, &splan, true));
+    if (!(splan->dia || (splan->slab && L > 1)))
+        splan = nullptr;
+    ST_TRY(get_plan(h, L, &plan));
+    const int nblk = cg_update_blocks((long long)h->m * L, h->num_cus);
+    const int cap = hist ? std::max(hist_cap, 0) : 0;
+    // partial rows of the two-dot folds are 2 L wide
+    ST_TRY(ensure_cg_workspace(h, L, nblk, std::max(plan->num_tiles, splan ? splan->num_tiles : 0), cap, 2 * L));
+    const size_t elems = (size_t)h->m * L;
+    if (elems > h->rhat_cap) {
+        dev_free(h->d_rhat);
+        h->rhat_cap = 0;
+        ST_TRY(dev_alloc(&h->d_rhat, elems));
+        h->rhat_cap = elems;
+    }
+    h->last_cg_kernel = "BiCGSTAB (2 SpMM + 5 passes)";
+    const int use_cap = hist ? cap : 0;
+    const int saved_cap = h->hist_cap;
+    h->hist_cap = use_cap;  // kernels record only what the caller asked for
+    int poison = 0;
+    ST_TRY(solve_prologue(h, {plan, splan}, &poison));
+    HIP_TRY(launch_bicgstab_init(h, d_b, d_x, L, tol, nblk));
+    ST_TRY(solve_poison_fill(h, poison));
+    auto iterate = [&](int) -> hipError_t { return launch_bicgstab_iteration(h, *plan, splan, d_x, L, nblk, tol); };
+    const int K = cg_batch_iters(h->m, h->nnz, L);
+    mspmv_status st = MSPMV_OK;
+    hipGraphExec_t exec = nullptr;
+    if (max_iters >= K && !(poison & MSPMV_POISON_LATE_ZERO)) {
+        const void *tk = nullptr;
+        std::memcpy(&tk, &tol, sizeof tk);
+        const std::vector<const void *> key = {
+            d_x, h->d_r, h->d_rhat, h->d_p0, h->d_p1, h->d_ap, h->d_partials, h->d_gtickets, h->d_scal, h->d_conv,
+            h->d_red, h->d_ctrl, h->d_hist, h->stream, plan, splan, tk,
+            reinterpret_cast<const void *>((intptr_t)L), reinterpret_cast<const void *>((intptr_t)nblk),
+            reinterpret_cast<const void *>((intptr_t)use_cap), reinterpret_cast<const void *>((intptr_t)K)};
+        st = solver_graph(h, SolverGraph{h->bicg_graph, h->bicg_exec, h->bicg_graph_key}, key, K, iterate, "BiCGSTAB");
+        exec = h->bicg_exec;
+    }
+    hipEvent_t evs[2] = {nullptr, nullptr};
+    if (st == MSPMV_OK)
+        st = solve_batches(h, K, max_iters, exec, poison, evs, "BiCGSTAB", iterate);
+    CgControl fin{};
+    ST_TRY(solve_collect(h, st, evs, saved_cap, use_cap, iters, hist, &fin, "BiCGSTAB"));
+    if (fin.breakdown) {
+        set_error("BiCGSTAB breakdown: a non-finite alpha, omega or beta in at least one column (frozen; the other "
+                  "columns were solved)");
+        return MSPMV_ERR_BREAKDOWN;
+    }
+    return MSPMV_OK;
+}
+
+static mspmv_status bicgstab_solve_dev(mspmv_handle_s *h, const double *d_b, double *d_x, int L, int max_iters,
+                                       double tol, int *iters, double *hist, int hist_cap)
+{
+    return solve_dev_groups(
+        h, d_b, d_x, L, iters, hist, hist_cap,
+        [&](const double *b, double *x, int w, int *it, double *hg, int cap) {
+            return bicgstab_solve_native(h, b, x, w, max_iters, tol, it, hg, cap);
+        },
+        "BiCGSTAB",
+        "BiCGSTAB breakdown: a non-finite alpha, omega or beta in at least one column (frozen; the other columns "
+        "were solved)");
+}
+
+// Host-pointer form of a device solve: B up, solve_dev(dB, dX), X down (also after a breakdown: the other
+// columns were solved).
+static mspmv_status solve_host(mspmv_handle h, const double *B, double *X, int L, int *iters,
+                               const std::function<mspmv_status(const double *, double *)> &solve_dev)
 {
     ST_TRY(check_handle(h));
     if (h->m == 0) {
@@ -1933,7 +2103,7 @@ static mspmv_status cg_solve_host(mspmv_handle h, const double *B, double *X, in
         st = MSPMV_ERR_HIP;
     }
     if (st == MSPMV_OK)
-        st = cg_solve_dev(h, dB, dX, L, max_iters, tol, iters, hist, hist_cap, hm, ic);
+        st = solve_dev(dB, dX);
     if ((st == MSPMV_OK || st == MSPMV_ERR_BREAKDOWN) && hipMemcpy(X, dX, bytes, hipMemcpyDeviceToHost) != hipSuccess) {
         set_error("X download failed");
         st = MSPMV_ERR_HIP;
@@ -1941,6 +2111,15 @@ static mspmv_status cg_solve_host(mspmv_handle h, const double *B, double *X, in
     dev_free(dB);
     dev_free(dX);
     return st;
+}
+
+static mspmv_status cg_solve_host(mspmv_handle h, const double *B, double *X, int L, int max_iters, double tol,
+                                  int *iters, double *hist, int hist_cap, mspmv_handle hm = nullptr,
+                                  mspmv_ic0 ic = nullptr)
+{
+    return solve_host(h, B, X, L, iters, [&](const double *dB, double *dX) {
+        return cg_solve_dev(h, dB, dX, L, max_iters, tol, iters, hist, hist_cap, hm, ic);
+    });
 }
 
 mspmv_status mspmv_dcg_single_dev(mspmv_handle h, const double *d_b, double *d_x, int max_iters, double tolerance,
@@ -2009,6 +2188,21 @@ mspmv_status mspmv_dcg_multi(mspmv_handle h, const double *B, double *X, int L, 
 {
     (void)kernel;
     return cg_solve_host(h, B, X, L, max_iters, tolerance, iters, max_err_hist, hist_cap);
+}
+
+mspmv_status mspmv_dbicgstab_multi_dev(mspmv_handle h, const double *d_B, double *d_X, int L, int max_iters,
+                                       double tolerance, int *iters, double *max_err_hist, int hist_cap)
+{
+    ST_TRY(check_handle(h));
+    return bicgstab_solve_dev(h, d_B, d_X, L, max_iters, tolerance, iters, max_err_hist, hist_cap);
+}
+
+mspmv_status mspmv_dbicgstab_multi(mspmv_handle h, const double *B, double *X, int L, int max_iters, double tolerance,
+                                   int *iters, double *max_err_hist, int hist_cap)
+{
+    return solve_host(h, B, X, L, iters, [&](const double *dB, double *dX) {
+        return bicgstab_solve_dev(h, dB, dX, L, max_iters, tolerance, iters, max_err_hist, hist_cap);
+    });
 }
 
 mspmv_status mspmv_dpcg_spai_multi_dev(mspmv_handle a, mspmv_handle m, const double *d_B, double *d_X, int L,

@@ -15,53 +15,7 @@
 
 namespace mspmv {
 
-// Deterministic multi-level "last block done" reduction of per-slot column partials.  The
-// caller has stored partials[slot][0..L) (agent scope, vmcnt drained) and synchronised.  Slots
-// form groups of kSlotGroup; the last of a group to arrive (one agent-scope ticket per group)
-// folds the group in slot order into the next level, whose groups fold the same way, until
-// one group remains: its last arriver holds the totals in s_out and returns true (exactly one
-// block does).  Tickets reset themselves for the next launch.  Why a tree of small groups on
-// separate 256-B lines: agent-scope atomics on one address serialise at the memory side
-// (~10 ns each), so 2 k blocks on one ticket cost ~22 us; fan-in 32 keeps each chain short.
-// RELEASE: the arrivals are agent-scope releases (ticket_arrive; k_fold_dot), else the drained-store form.
-template <int L, bool RELEASE = false>
-__device__ __forceinline__ bool reduce_slots(double *partials, unsigned *tickets, int slot, int nslots,
-                                             double *s_tmp, double *s_out, int *s_flag, CgControl *ctrl)
-{
-    const int tid = threadIdx.x;
-    double *lvl = partials;
-    int idx = slot, count = nslots;
-    for (;;) {
-        const int g = idx / kSlotGroup;
-        const int ngroups = (count + kSlotGroup - 1) / kSlotGroup;
-        const int gsize = min(kSlotGroup, count - g * kSlotGroup);
-        unsigned *tk = &tickets[(size_t)g * kTicketStride];
-        if (tid == 0)
-            *s_flag = take_ticket<RELEASE>(tk, gsize, ctrl);
-        __syncthreads();
-        if (!*s_flag)
-            return false;
-        fold_cols<L>(lvl + (size_t)g * kSlotGroup * L, gsize, s_tmp, s_out);
-        if (tid == 0)
-            __hip_atomic_store(tk, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (ngroups == 1)
-            return true;
-        double *next = lvl + (size_t)count * L;
-        if (tid < L) {
-            store_sc1(&next[(size_t)g * L + tid], s_out[tid]);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __syncthreads();
-        tickets += (size_t)ngroups * kTicketStride;
-        lvl = next;
-        idx = g;
-        count = ngroups;
-    }
-}
-
-// Per-column state in CgVecArgs::conv (and the tile kernels' conv): 0 iterating, 1 converged (the
-// reference's converged[] mask), kConvBroken = p.Ap gave a non-finite alpha (frozen).
-constexpr unsigned char kConvBroken = 2;
+// (reduce_slots, kConvBroken, colpair_block_reduce, for_pairs: mspmv_device.h, shared with mspmv_bicgstab.hip)
 
 // What the fold's last block derives from the totals (k_fold_dot `mode`).
 enum : int { kFoldDot = 0, kFoldCgAlpha = 1, kFoldPcgAlpha = 2, kFoldPcgBeta = 3, kFoldPcgInit = 4 };
@@ -153,68 +107,7 @@ __global__ __launch_bounds__(kBlock) void k_fold_dot(const double *part, int T, 
 // ------------------------------------------------------------------------------------------
 // CG: init and the fused update (x += alpha p; r += (-alpha) Ap; r.r; stop test; beta)
 // ------------------------------------------------------------------------------------------
-// Column-pair partial sums of a grid-stride loop over n*L elements viewed as pairs.  Each
-// thread always meets the same column pair because the stride (in pairs) is a multiple of
-// L/2 (L/2 divides 256).  For L == 1 the "pair" is two consecutive rows of one column.
-template <int L>
-__device__ __forceinline__ void colpair_block_reduce(double2 v, double2 (*s_red2)[L > 1 ? L / 2 : 1],
-                                                     double *partials_row)
-{
-    constexpr int GL = L > 1 ? L / 2 : 1;
-    const int tid = threadIdx.x;
-    if (L == 1)
-        v.x += v.y;
-#pragma unroll
-    for (int off = 32; off >= GL; off >>= 1) {
-        v.x += __shfl_xor(v.x, off);
-        if (L > 1)
-            v.y += __shfl_xor(v.y, off);
-    }
-    if ((tid & 63) < GL)
-        s_red2[tid >> 6][tid & 63] = v;
-    __syncthreads();
-    if (tid < GL) {
-        double2 s = s_red2[0][tid];
-#pragma unroll
-        for (int w = 1; w < kBlock / 64; ++w) {
-            s.x += s_red2[w][tid].x;
-            s.y += s_red2[w][tid].y;
-        }
-        if (L == 1) {
-            store_sc1(&partials_row[0], s.x);
-        } else {
-            store_sc1(&partials_row[2 * tid], s.x);
-            store_sc1(&partials_row[2 * tid + 1], s.y);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __syncthreads();
-}
-
 // (CgVecArgs: mspmv_internal.h)
-
-// Chunk c (of kBlock x gridDim elements, element i = c * stride + i0) visited at step k: first to
-// last, or last to first (CgVecArgs::rev).
-__device__ __forceinline__ long long sweep_index(long long k, long long nchunks, long long stride, long long i0, int rev)
-{
-    return (rev ? nchunks - 1 - k : k) * stride + i0;
-}
-
-// The pairs a thread of a streaming CG kernel visits, in order: grid-stride chunks (the whole grid
-// sweeps one chunk after another, rev: last chunk first).  (One contiguous slice per workgroup, the
-// read ceiling's layout, measured even: CG multi L = 8 0.920-0.921 vs 0.916-0.919 ms, r03aa.)
-template <int GL, typename F>
-__device__ __forceinline__ void for_pairs(long long npairs, int rev, F &&f)
-{
-    const long long stride = (long long)gridDim.x * kBlock;
-    const long long i0 = (long long)blockIdx.x * kBlock + threadIdx.x;
-    const long long nch = (npairs + stride - 1) / stride;
-    for (long long k = 0; k < nch; ++k) {
-        const long long i = sweep_index(k, nch, stride, i0, rev);
-        if (i < npairs)
-            f(i);
-    }
-}
 
 // x = 0, r = p0 = b; rs_old_j = r_j.r_j, b_norm_j = sqrt(b_j.b_j) (no_pretreatment.hpp:61-79,
 // single_strategy.hpp:120-131).
@@ -960,6 +853,19 @@ bool dia_dot_fused()
     return !(e && *e && atoi(e) == 0);
 }
 
+// Y = A X inside a solver's iteration: the plain L-wide product on the plan the solve chose for it (splan: the
+// handle's offset-window or column-slab plan, else null -> the merge tiles of `plan`), with the control word,
+// so the launch returns at once when the solve has stopped.  The split CG and BiCGSTAB launch it.
+hipError_t launch_solver_product(mspmv_handle_s *h, const TilePlan &plan, const TilePlan *splan, const double *d_X,
+                                 double *d_Y, int L)
+{
+    if (splan && splan->dia)
+        return launch_dia(h, *splan, d_X, d_Y, L, L, h->d_ctrl);
+    if (splan && splan->slab)
+        return launch_slab_mm(h, *splan, d_X, d_Y, L, L, h->d_ctrl);
+    return launch_spmm_tile_only(h, plan, d_X, d_Y, L, 0, h->d_ctrl);
+}
+
 // splan: the plan the solve chose for the plain L-wide product (cg_solve_native: the offset-window or
 // column-slab plan, else null -> the tiles of `plan`); dot_fused: the window SpMM takes p.Ap in its dot
 // mode (resolved once per solve, and part of the CG graph's key).
@@ -982,7 +888,6 @@ static hipError_t launch_cg_iteration_split(mspmv_handle_s *h, const TilePlan &p
     if (e != hipSuccess)
         return e;
     const TilePlan *dp = splan && splan->dia ? splan : nullptr;
-    const TilePlan *sp = splan && splan->slab ? splan : nullptr;
     if (dp && dot_fused) {
         // offset windows (mspmv_dia.hip) in dot mode: Ap and one p.Ap partial per window, folded with the
         // non-finite-alpha stop -- no separate pass over p and Ap
@@ -996,15 +901,8 @@ static hipError_t launch_cg_iteration_split(mspmv_handle_s *h, const TilePlan &p
         // workgroups per CU, and never spills), stopped by the control word, then p.Ap in one
         // streaming pass over p and Ap with the fold's breakdown checks (k_pcg_dot mode 2)
         // (on the offset-window or column-slab plan when the handle's plain L-wide product took one)
-        if (dp) {
-            if ((e = launch_dia(h, *dp, h->d_p0, h->d_ap, L, L, h->d_ctrl)) != hipSuccess)
-                return e;
-        } else if (sp) {
-            if ((e = launch_slab_mm(h, *sp, h->d_p0, h->d_ap, L, L, h->d_ctrl)) != hipSuccess)
-                return e;
-        } else if ((e = launch_spmm_tile_only(h, plan, h->d_p0, h->d_ap, L, 0, h->d_ctrl)) != hipSuccess) {
+        if ((e = launch_solver_product(h, plan, splan, h->d_p0, h->d_ap, L)) != hipSuccess)
             return e;
-        }
         CgVecArgs vd = va;
         vd.r = h->d_p0;
         vd.p = h->d_ap;

@@ -1,5 +1,5 @@
-// Device helpers shared by the tile kernels (mspmv_kernels.hip), the CG passes (mspmv_cg_passes.hip)
-// and the column-slab SpMV (mspmv_slab.hip): agent-scope stores and loads, the XCD-contiguous tile mapping, and the closing of
+// Device helpers shared by the tile kernels (mspmv_kernels.hip), the CG and BiCGSTAB passes (mspmv_cg_passes.hip,
+// mspmv_bicgstab.hip) and the column-slab SpMV (mspmv_slab.hip): agent-scope stores and loads, the XCD-contiguous tile mapping, and the closing of
 // rows split between tiles.  Included by HIP sources only.
 #pragma once
 #include "mspmv_internal.h"
@@ -209,6 +209,116 @@ __device__ __forceinline__ bool take_ticket(unsigned *tk, int gsize, CgControl *
     if (faulted && ctrl && !__hip_atomic_load(&ctrl->fault_no_stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
         __hip_atomic_store(&ctrl->done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return false;
+}
+
+// ---- the streaming solver passes' folds (mspmv_cg_passes.hip, mspmv_bicgstab.hip) ----
+// Deterministic multi-level "last block done" reduction of per-slot column partials.  The
+// caller has stored partials[slot][0..L) (agent scope, vmcnt drained) and synchronised.  Slots
+// form groups of kSlotGroup; the last of a group to arrive (one agent-scope ticket per group)
+// folds the group in slot order into the next level, whose groups fold the same way, until
+// one group remains: its last arriver holds the totals in s_out and returns true (exactly one
+// block does).  Tickets reset themselves for the next launch.  Why a tree of small groups on
+// separate 256-B lines: agent-scope atomics on one address serialise at the memory side
+// (~10 ns each), so 2 k blocks on one ticket cost ~22 us; fan-in 32 keeps each chain short.
+// RELEASE: the arrivals are agent-scope releases (ticket_arrive; k_fold_dot), else the drained-store form.
+template <int L, bool RELEASE = false>
+__device__ __forceinline__ bool reduce_slots(double *partials, unsigned *tickets, int slot, int nslots,
+                                             double *s_tmp, double *s_out, int *s_flag, CgControl *ctrl)
+{
+    const int tid = threadIdx.x;
+    double *lvl = partials;
+    int idx = slot, count = nslots;
+    for (;;) {
+        const int g = idx / kSlotGroup;
+        const int ngroups = (count + kSlotGroup - 1) / kSlotGroup;
+        const int gsize = min(kSlotGroup, count - g * kSlotGroup);
+        unsigned *tk = &tickets[(size_t)g * kTicketStride];
+        if (tid == 0)
+            *s_flag = take_ticket<RELEASE>(tk, gsize, ctrl);
+        __syncthreads();
+        if (!*s_flag)
+            return false;
+        fold_cols<L>(lvl + (size_t)g * kSlotGroup * L, gsize, s_tmp, s_out);
+        if (tid == 0)
+            __hip_atomic_store(tk, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (ngroups == 1)
+            return true;
+        double *next = lvl + (size_t)count * L;
+        if (tid < L) {
+            store_sc1(&next[(size_t)g * L + tid], s_out[tid]);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        __syncthreads();
+        tickets += (size_t)ngroups * kTicketStride;
+        lvl = next;
+        idx = g;
+        count = ngroups;
+    }
+}
+
+// Per-column state in CgVecArgs::conv (and the tile kernels' conv): 0 iterating, 1 converged (the
+// reference's converged[] mask), kConvBroken = p.Ap gave a non-finite alpha (frozen).
+constexpr unsigned char kConvBroken = 2;
+
+// Column-pair partial sums of a grid-stride loop over n*L elements viewed as pairs.  Each
+// thread always meets the same column pair because the stride (in pairs) is a multiple of
+// L/2 (L/2 divides 256).  For L == 1 the "pair" is two consecutive rows of one column.
+template <int L>
+__device__ __forceinline__ void colpair_block_reduce(double2 v, double2 (*s_red2)[L > 1 ? L / 2 : 1],
+                                                     double *partials_row)
+{
+    constexpr int GL = L > 1 ? L / 2 : 1;
+    const int tid = threadIdx.x;
+    if (L == 1)
+        v.x += v.y;
+#pragma unroll
+    for (int off = 32; off >= GL; off >>= 1) {
+        v.x += __shfl_xor(v.x, off);
+        if (L > 1)
+            v.y += __shfl_xor(v.y, off);
+    }
+    if ((tid & 63) < GL)
+        s_red2[tid >> 6][tid & 63] = v;
+    __syncthreads();
+    if (tid < GL) {
+        double2 s = s_red2[0][tid];
+#pragma unroll
+        for (int w = 1; w < kBlock / 64; ++w) {
+            s.x += s_red2[w][tid].x;
+            s.y += s_red2[w][tid].y;
+        }
+        if (L == 1) {
+            store_sc1(&partials_row[0], s.x);
+        } else {
+            store_sc1(&partials_row[2 * tid], s.x);
+            store_sc1(&partials_row[2 * tid + 1], s.y);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __syncthreads();
+}
+
+// Chunk c (of kBlock x gridDim elements, element i = c * stride + i0) visited at step k: first to
+// last, or last to first (CgVecArgs::rev).
+__device__ __forceinline__ long long sweep_index(long long k, long long nchunks, long long stride, long long i0, int rev)
+{
+    return (rev ? nchunks - 1 - k : k) * stride + i0;
+}
+
+// The pairs a thread of a streaming CG kernel visits, in order: grid-stride chunks (the whole grid
+// sweeps one chunk after another, rev: last chunk first).  (One contiguous slice per workgroup, the
+// read ceiling's layout, measured even: CG multi L = 8 0.920-0.921 vs 0.916-0.919 ms, r03aa.)
+template <int GL, typename F>
+__device__ __forceinline__ void for_pairs(long long npairs, int rev, F &&f)
+{
+    const long long stride = (long long)gridDim.x * kBlock;
+    const long long i0 = (long long)blockIdx.x * kBlock + threadIdx.x;
+    const long long nch = (npairs + stride - 1) / stride;
+    for (long long k = 0; k < nch; ++k) {
+        const long long i = sweep_index(k, nch, stride, i0, rev);
+        if (i < npairs)
+            f(i);
+    }
 }
 
 // Consumer-side reduction (single-RHS pipelined CG).  A producer kernel leaves one partial per

@@ -202,6 +202,8 @@ struct CgScalars {
     double pAp;
     double rs_new;
     double rs_par[2];  // single-RHS pipelined CG: r.r of iteration k at [k & 1] (k_spmv_tile MODE 1)
+    double omega;      // BiCGSTAB (mspmv_bicgstab.hip): t.s / t.t of the running iteration
+    double rho;        // BiCGSTAB: rhat.r entering the iteration
 };
 
 struct CgControl {
@@ -256,6 +258,8 @@ struct mspmv_handle_s {
     // CG workspace (grown on demand)
     size_t cg_cap_elems = 0;
     double *d_r = nullptr, *d_p0 = nullptr, *d_p1 = nullptr, *d_ap = nullptr;
+    double *d_rhat = nullptr;  // BiCGSTAB's shadow residual (allocated by that solver only)
+    size_t rhat_cap = 0;
     double *d_partials = nullptr;
     size_t partials_cap = 0;
     double *d_partials_b = nullptr;  // single-RHS pipelined CG: r.r partials of init / update (<= kUpdateMaxBlocks)
@@ -285,6 +289,10 @@ struct mspmv_handle_s {
     hipGraph_t cg_graph = nullptr;
     hipGraphExec_t cg_exec = nullptr;
     std::vector<const void *> cg_graph_key;
+    // ... and BiCGSTAB's (bicgstab_solve_native), cached apart so neither solver evicts the other's
+    hipGraph_t bicg_graph = nullptr;
+    hipGraphExec_t bicg_exec = nullptr;
+    std::vector<const void *> bicg_graph_key;
     // timing
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double last_tile_kernel_ms = 0.0;
@@ -504,6 +512,16 @@ hipError_t launch_spmv_tile_stamped(mspmv_handle_s *h, const TilePlan &plan, con
 hipError_t launch_cg_iteration(mspmv_handle_s *h, const TilePlan &plan, const TilePlan *splan, bool dot_fused,
                                double *d_x, int L, int parity, int nblk, double tol);
 int cg_update_blocks(long long elems, int num_cus);
+// The plain L-wide product of a solver's iteration on the solve's plan (splan: offset windows or column slabs,
+// else null -> the merge tiles of plan), stopped by the handle's control word
+hipError_t launch_solver_product(mspmv_handle_s *h, const TilePlan &plan, const TilePlan *splan, const double *d_X,
+                                 double *d_Y, int L);
+// BiCGSTAB (mspmv_bicgstab.hip): init (X = 0, R = Rhat = P = B, rho = B.B) and one iteration -- V = A P, the
+// rhat.v pass, the s pass, T = A s, the t.t / t.s pass, the update pass (stop test, beta), the p pass.  R, P, V,
+// T live in h->d_r, d_p0, d_ap, d_p1; Rhat in h->d_rhat.  Partial rows are 2 L wide.
+hipError_t launch_bicgstab_init(mspmv_handle_s *h, const double *d_b, double *d_x, int L, double tol, int nblk);
+hipError_t launch_bicgstab_iteration(mspmv_handle_s *h, const TilePlan &plan, const TilePlan *splan, double *d_x, int L,
+                                     int nblk, double tol);
 // Iterations per CG batch / graph replay for an m-row, nnz-nonzero matrix and L columns (mspmv_api.hip).
 int cg_batch_iters(long long m, long long nnz, int L);
 // Pipelined single-RHS CG (L == 1 unless MSPMV_CG_SPLIT=1): init (x = 0, r = p0 = b, b.b

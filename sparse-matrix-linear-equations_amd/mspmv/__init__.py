@@ -98,6 +98,8 @@ _SIGS = {
     "mspmv_cg_resident_stamps": (_I, [_P, _P, _P, _I, _D, _PI, _P, _I, _PI]),
     "mspmv_dcg_multi": (_I, [_P, _P, _P, _I, _I, _D, _I, _PI, _P, _I]),
     "mspmv_dcg_multi_dev": (_I, [_P, _P, _P, _I, _I, _D, _I, _PI, _P, _I]),
+    "mspmv_dbicgstab_multi": (_I, [_P, _P, _P, _I, _I, _D, _PI, _P, _I]),
+    "mspmv_dbicgstab_multi_dev": (_I, [_P, _P, _P, _I, _I, _D, _PI, _P, _I]),
     "mspmv_spai_values": (_I, [ctypes.POINTER(_CsrD), _P]),
     "mspmv_ic0_nnz": (_I, [ctypes.POINTER(_CsrD), _PI]),
     "mspmv_ic0_factor": (_I, [ctypes.POINTER(_CsrD), _P, _P, _P, _PD]),
@@ -611,6 +613,31 @@ class GpuCsr:
         _check(st, "dcg_multi_dev", allow=(4,))
         return it.value, hist[: min(it.value, hist_cap)], st
 
+    def bicgstab(self, B: np.ndarray, max_iters: int, tolerance: float, hist_cap: int = 0,
+                 allow_fault: bool = False):
+        """Multi-RHS BiCGSTAB for a square, possibly nonsymmetric matrix (mspmv_dbicgstab_multi):
+        (X, iterations, history, status); a per-column breakdown is returned, not raised, as cg_multi's."""
+        B = np.ascontiguousarray(B, np.float64)
+        if B.ndim == 1:
+            B = B.reshape(-1, 1)
+        L = B.shape[1]
+        X = np.empty_like(B)
+        it = ctypes.c_int()
+        hist = np.zeros(max(hist_cap, 1), np.float64)
+        st = lib.mspmv_dbicgstab_multi(self.h, _ptr(B), _ptr(X), L, max_iters, tolerance, ctypes.byref(it),
+                                       _ptr(hist) if hist_cap else None, hist_cap)
+        _check(st, "dbicgstab_multi", allow=(4, FAULT) if allow_fault else (4,))
+        return X, it.value, hist[: min(it.value, hist_cap)], st
+
+    def bicgstab_dev(self, dB: DeviceBuffer, dX: DeviceBuffer, L: int, max_iters: int, tolerance: float,
+                     hist_cap: int = 0):
+        it = ctypes.c_int()
+        hist = np.zeros(max(hist_cap, 1), np.float64)
+        st = lib.mspmv_dbicgstab_multi_dev(self.h, dB.ptr, dX.ptr, L, max_iters, tolerance, ctypes.byref(it),
+                                           _ptr(hist) if hist_cap else None, hist_cap)
+        _check(st, "dbicgstab_multi_dev", allow=(4,))
+        return it.value, hist[: min(it.value, hist_cap)], st
+
     def pcg_spai(self, m: "GpuCsr", B: np.ndarray, max_iters: int, tolerance: float, hist_cap: int = 0):
         """SPAISolveMultiple with the preconditioner M's handle `m` (mspmv_dpcg_spai_multi)."""
         B = np.ascontiguousarray(B, np.float64)
@@ -773,6 +800,21 @@ def CGSolveMultiple(a: CsrMatrix, B, X, num_vectors: int, max_iters: int, tolera
     cap = max_iters if max_errors is not None else 0
     Xs, it, hist, st = _gpu(a).cg_multi(Bm, max_iters, tolerance, kernel_type, hist_cap=cap)
     _note_breakdown(st, "CGSolveMultiple")
+    X[:] = Xs.reshape(-1)
+    if max_errors is not None:
+        max_errors.clear()
+        max_errors.extend(hist.tolist())
+    return it
+
+
+def BiCGStabSolveMultiple(a: CsrMatrix, B, X, num_vectors: int, max_iters: int, tolerance: float,
+                          max_errors: Optional[list] = None) -> int:
+    """Multi-RHS BiCGSTAB on flat interleaved n x num_vectors panels, in CGSolveMultiple's calling form (no
+    reference counterpart: the reference has CG solvers only); returns the iteration count."""
+    Bm = np.asarray(B, np.float64).reshape(a.num_rows, num_vectors)
+    cap = max_iters if max_errors is not None else 0
+    Xs, it, hist, st = _gpu(a).bicgstab(Bm, max_iters, tolerance, hist_cap=cap)
+    _note_breakdown(st, "BiCGStabSolveMultiple")
     X[:] = Xs.reshape(-1)
     if max_errors is not None:
         max_errors.clear()

@@ -5,8 +5,11 @@
 //   --multi: cpu_multicg's CGSolveMultiple leg (cpu_multicg.cpp:106-210): L lock-step RHS,
 //     "Min time / Iters / GFLOPS" line and the per-iteration max error CSV (:67-86).
 //
+//   --solver=bicgstab: the same two legs on mspmv_dbicgstab_multi (nonsymmetric matrices; the single leg
+//     solves its vectors one after another at L = 1).  Default --solver=cg.
+//
 //   mspmv_cg --mtx=<file> [--multi] [--num_vectors=16] [--max_iters=N] [--tolerance=1e-5]
-//            [--timing_iters=1] [--output=<csv>] [--seed=42] [--device=0] [--quiet]
+//            [--timing_iters=1] [--output=<csv>] [--seed=42] [--device=0] [--quiet] [--solver=cg|bicgstab]
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -68,6 +71,13 @@ int main(int argc, char **argv)
     if (arg(argc, argv, "timing_iters", s)) timing = std::max(1, atoi(s.c_str()));
     if (arg(argc, argv, "seed", s)) seed = (unsigned)atoi(s.c_str());
     if (arg(argc, argv, "device", s)) device = atoi(s.c_str());
+    std::string solver = "cg";
+    arg(argc, argv, "solver", solver);
+    if (solver != "cg" && solver != "bicgstab") {
+        fprintf(stderr, "--solver must be cg or bicgstab\n");
+        return 1;
+    }
+    const bool bicg = solver == "bicgstab";
     if (mtx.empty()) {
         fprintf(stderr, "Usage: %s --mtx=<filename> [--multi] [options]\n", argv[0]);
         return 1;
@@ -90,7 +100,8 @@ int main(int argc, char **argv)
     for (int i = 0; i < m; ++i)
         nb += B[i] * B[i];
     const double threshold = std::sqrt(nb) * tol;  // calculate_threshold, cpu_singlecg.cpp:22-34
-    const double flops1 = 2.0 * nnz + 10.0 * m;
+    // per iteration and column: CG one product and 10 vector flops per row; BiCGSTAB two products and 22
+    const double flops1 = bicg ? 4.0 * nnz + 22.0 * m : 2.0 * nnz + 10.0 * m;
     const std::string name = base_name(mtx);
     double min_ms = std::numeric_limits<double>::max();
     long long iters_min = 0;
@@ -101,17 +112,21 @@ int main(int argc, char **argv)
         if (!multi) {
             for (int v = 0; v < L; ++v) {  // column blocks B[v*n .. ] (single_strategy.hpp:219-226)
                 int it = 0;
-                st = mspmv_dcg_single(h, &B[(size_t)v * m], &X[(size_t)v * m], max_iters, threshold, &it, nullptr, 0);
+                st = bicg ? mspmv_dbicgstab_multi(h, &B[(size_t)v * m], &X[(size_t)v * m], 1, max_iters, threshold, &it,
+                                                  nullptr, 0)
+                          : mspmv_dcg_single(h, &B[(size_t)v * m], &X[(size_t)v * m], max_iters, threshold, &it, nullptr, 0);
                 if (st != MSPMV_OK && st != MSPMV_ERR_BREAKDOWN)
-                    die("mspmv_dcg_single", st);
+                    die(bicg ? "mspmv_dbicgstab_multi" : "mspmv_dcg_single", st);
                 total += it;
             }
         } else {
             int it = 0;
-            st = mspmv_dcg_multi(h, B.data(), X.data(), L, max_iters, threshold, MSPMV_NONZERO_SPLIT, &it,
-                                 t == 0 ? hist.data() : nullptr, t == 0 ? max_iters : 0);
+            st = bicg ? mspmv_dbicgstab_multi(h, B.data(), X.data(), L, max_iters, threshold, &it,
+                                              t == 0 ? hist.data() : nullptr, t == 0 ? max_iters : 0)
+                      : mspmv_dcg_multi(h, B.data(), X.data(), L, max_iters, threshold, MSPMV_NONZERO_SPLIT, &it,
+                                        t == 0 ? hist.data() : nullptr, t == 0 ? max_iters : 0);
             if (st != MSPMV_OK && st != MSPMV_ERR_BREAKDOWN)
-                die("mspmv_dcg_multi", st);
+                die(bicg ? "mspmv_dbicgstab_multi" : "mspmv_dcg_multi", st);
             total = it;
             if (t == 0)
                 hist.resize(std::min<size_t>(hist.size(), (size_t)it));
@@ -124,15 +139,16 @@ int main(int argc, char **argv)
             iters_min = total;
         }
     }
+    const char *method = bicg ? "GPU_BICGSTAB_LOOP" : "GPU_SINGLE_LOOP";
     if (!multi) {
         const double gflops = flops1 * (double)iters_min / (min_ms / 1000.0) / 1e9;
-        printf("    %s, L=%d, method=GPU_SINGLE_LOOP: %.3f ms, %lld iters, %.2f GFLOPS\n", name.c_str(), L, min_ms,
+        printf("    %s, L=%d, method=%s: %.3f ms, %lld iters, %.2f GFLOPS\n", name.c_str(), L, method, min_ms,
                iters_min, gflops);
         if (out_csv.empty())
             out_csv = "data/simple_gflops/" + name + "_gflops.csv";
         if (FILE *f = fopen(out_csv.c_str(), "w")) {
-            fprintf(f, "matrix_name,kernel,num_vectors,min_ms,gflops,iterations\n%s,GPU_SINGLE_LOOP,%d,%.3f,%.2f,%lld\n",
-                    name.c_str(), L, min_ms, gflops, iters_min);
+            fprintf(f, "matrix_name,kernel,num_vectors,min_ms,gflops,iterations\n%s,%s,%d,%.3f,%.2f,%lld\n",
+                    name.c_str(), method, L, min_ms, gflops, iters_min);
             fclose(f);
         } else {
             fprintf(stderr, "Error: Cannot open file %s for writing\n", out_csv.c_str());

@@ -1,0 +1,257 @@
+"""GPU: multi-RHS BiCGSTAB (mspmv_dbicgstab_multi, csrc/mspmv_bicgstab.hip) against the numpy
+restatement of test_bicgstab.py (its fsum order is the reference; the other two orders measure how far a
+legitimate reordering of the dot products moves the iterates)."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import test_bicgstab as tb
+from test_bicgstab import TOL
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIN = os.path.join(ROOT, "sparse-matrix-linear-equations_amd", "mspmv", "bin")
+BREAKDOWN = 4
+MAX_ITERS = 200
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _need_gpu(gpu_available):
+    return gpu_available
+
+
+def csr(mspmv, a):
+    ro, ci, va = a
+    return mspmv.CsrMatrix.from_arrays(len(ro) - 1, ro, ci, va)
+
+
+def check_counts(it, ref):
+    counts = [ref[o][1] for o in tb.ORDERS]
+    assert min(counts) - 1 <= it <= max(counts) + 1, (it, counts)
+
+
+def check_true_residual(a, B, X, cols=None):
+    tr = tb.true_residual(a, B, X)
+    tr = tr if cols is None else tr[cols]
+    print(f"worst true residual {tr.max():.3e}")
+    assert np.all(np.isfinite(X)) and np.all(tr <= 2 * TOL), tr
+
+
+def check_history(name, hist, ref):
+    """randdd: the project's CG bar, 1e-10.  convdiff: BiCGSTAB's residual is erratic there and the
+    restatement's own summation orders drift apart, so the bar at iteration k is ten times the largest
+    spread of the other two orders from the reference up to k, plus 64 ulp of the largest entry."""
+    h_ref = ref["fsum"][2]
+    k = min(len(hist), len(h_ref))
+    err = np.abs(hist[:k] - h_ref[:k])
+    if name == "randdd":
+        print(f"history: worst |h - h_ref| {err.max():.3e} (bar 1e-10)")
+        assert np.all(err <= 1e-10), err.max()
+        return
+    spread = np.zeros(k)
+    for o in tb.ORDERS[1:]:
+        h = ref[o][2]
+        q = min(k, len(h))
+        spread[:q] = np.maximum(spread[:q], np.abs(h[:q] - h_ref[:q]))
+    bar = 10.0 * np.maximum.accumulate(spread) + 64.0 * 2.0 ** -53 * h_ref.max()
+    print(f"history: worst |h - h_ref| / bar {np.max(err / bar):.3g}")
+    assert np.all(err <= bar), np.max(err / bar)
+
+
+@pytest.mark.parametrize("L", [1, 2, 8, 6, 16])
+@pytest.mark.parametrize("name", ["convdiff30", "randdd"])
+def test_against_restatement(mspmv, name, L):
+    a = tb.matrix(name)
+    n = len(a[0]) - 1
+    B = tb.rhs(n, L)
+    ref = tb.reference(name, L)
+    with mspmv.GpuCsr(csr(mspmv, a), device=0) as g:
+        X, it, hist, st = g.bicgstab(B, MAX_ITERS, TOL, hist_cap=MAX_ITERS)
+        assert g.cg_kernel_name() == "BiCGSTAB (2 SpMM + 5 passes)"
+        X2, it2, hist2, st2 = g.bicgstab(B, MAX_ITERS, TOL, hist_cap=MAX_ITERS)  # the cached graph, replayed
+    assert st == 0 and st2 == 0
+    check_counts(it, ref)
+    assert len(hist) == it
+    check_true_residual(a, B, X)
+    X_ref = ref["fsum"][0]
+    cond = np.linalg.cond(tb.dense(a))
+    err = np.linalg.norm(X - X_ref, axis=0) / np.linalg.norm(X_ref, axis=0)
+    print(f"worst |X - X_ref| / |X_ref| {err.max():.3e} (bar {2 * TOL * cond:.3e})")
+    assert np.all(err <= 2 * TOL * cond)
+    check_history(name, hist, ref)
+    assert it2 == it
+    np.testing.assert_array_equal(X2, X)
+    np.testing.assert_array_equal(hist2, hist)
+
+
+@pytest.mark.parametrize("L", [8, 16])
+def test_two_level_fold(mspmv, L):
+    """convdiff(60, 47): 45 (L = 8) and 89 (L = 16) update blocks, so the folds run two levels."""
+    a = tb.matrix("convdiff60")
+    B = tb.rhs(len(a[0]) - 1, L)
+    ref = tb.reference("convdiff60", L)
+    with mspmv.GpuCsr(csr(mspmv, a), device=0) as g:
+        X, it, hist, st = g.bicgstab(B, MAX_ITERS, TOL, hist_cap=MAX_ITERS)
+    assert st == 0
+    check_counts(it, ref)
+    check_true_residual(a, B, X)
+    check_history("convdiff60", hist, ref)
+
+
+@pytest.mark.parametrize("L", [1, 8])
+def test_default_plan_offset_windows(mspmv, monkeypatch, L):
+    """Without MSPMV_DIA=0 the stencil takes the offset-window plan, and the solver's two products run on it."""
+    monkeypatch.delenv("MSPMV_DIA", raising=False)
+    a = tb.matrix("convdiff60")
+    B = tb.rhs(len(a[0]) - 1, L)
+    ref = tb.reference("convdiff60", L)
+    with mspmv.GpuCsr(csr(mspmv, a), device=0) as g:
+        X, it, hist, st = g.bicgstab(B, MAX_ITERS, TOL, hist_cap=MAX_ITERS)
+        kernel = g.spmm_kernel_name(L)
+    if "k_spmm_dia" not in kernel:
+        pytest.skip(f"the plain L = {L} product of this matrix does not take the offset windows ({kernel})")
+    assert st == 0
+    check_counts(it, ref)
+    check_true_residual(a, B, X)
+    check_history("convdiff60", hist, ref)
+
+
+def test_lucky_half_step(mspmv):
+    """A = 2I: s is exactly 0 after the half-step, T.T = 0 gives omega = 0 (not a breakdown), x = b/2."""
+    B = tb.rhs(300, 4)
+    with mspmv.GpuCsr(csr(mspmv, tb.identity(300, 2.0)), device=0) as g:
+        X, it, hist, st = g.bicgstab(B, 50, TOL, hist_cap=50)
+    assert st == 0 and it == 1
+    np.testing.assert_array_equal(X, B / 2)
+
+
+def test_zero_rhs_column(mspmv):
+    a = tb.matrix("randdd")
+    B = tb.rhs(777, 4).copy()
+    B[:, 2] = 0.0
+    with mspmv.GpuCsr(csr(mspmv, a), device=0) as g:
+        X, it, hist, st = g.bicgstab(B, MAX_ITERS, TOL, hist_cap=MAX_ITERS)
+    assert st == BREAKDOWN
+    assert np.all(X[:, 2] == 0.0) and np.all(np.isfinite(X))
+    check_true_residual(a, B[:, [0, 1, 3]], X[:, [0, 1, 3]])
+    _, it_ref, h_ref, st_ref, _ = tb.bicgstab_ref(a, B, MAX_ITERS, TOL)
+    assert st_ref == BREAKDOWN and abs(it - it_ref) <= 1
+    k = min(len(hist), len(h_ref))
+    assert np.all(np.abs(hist[:k] - h_ref[:k]) <= 1e-10)
+
+
+def test_max_iters(mspmv):
+    """max_iters below a batch runs ungraphed and stops there; its history is the long run's head."""
+    a = tb.matrix("convdiff30")
+    B = tb.rhs(930, 4)
+    with mspmv.GpuCsr(csr(mspmv, a), device=0) as g:
+        _, it50, h50, st50 = g.bicgstab(B, 50, TOL, hist_cap=50)
+        X5, it5, h5, st5 = g.bicgstab(B, 5, TOL, hist_cap=50)
+        X0, it0, h0, st0 = g.bicgstab(B, 0, TOL, hist_cap=50)
+    assert st50 == 0 and st5 == 0 and st0 == 0
+    assert it5 == 5 and len(h5) == 5 and it50 > 5
+    np.testing.assert_array_equal(h5, h50[:5])
+    assert it0 == 0 and len(h0) == 0 and np.all(X0 == 0.0)
+
+
+def test_cu_limit_bit_identical(mspmv):
+    a = tb.matrix("convdiff60")
+    B = tb.rhs(len(a[0]) - 1, 8)
+    with mspmv.GpuCsr(csr(mspmv, a), device=0) as g:
+        X, it, hist, st = g.bicgstab(B, MAX_ITERS, TOL, hist_cap=MAX_ITERS)
+        g.set_cu_limit(64)
+        Xm, itm, histm, stm = g.bicgstab(B, MAX_ITERS, TOL, hist_cap=MAX_ITERS)
+    assert st == 0 and stm == 0 and itm == it
+    np.testing.assert_array_equal(Xm, X)
+    np.testing.assert_array_equal(histm, hist)
+
+
+def test_poisoned_tickets(mspmv):
+    """Fold tickets dirty when the iterations begin: an arrival draws past its group, the solve stops
+    with MSPMV_ERR_FAULT; the next solve starts from re-zeroed tickets and is clean."""
+    a = tb.matrix("randdd")
+    B = tb.rhs(777, 8)
+    ref = tb.reference("randdd", 8)
+    with mspmv.GpuCsr(csr(mspmv, a), device=0) as g:
+        g.test_poison_tickets(32)
+        with pytest.raises(mspmv.MspmvError) as ei:
+            g.bicgstab(B, MAX_ITERS, TOL, hist_cap=MAX_ITERS)
+        assert ei.value.status == mspmv.FAULT
+        X, it, hist, st = g.bicgstab(B, MAX_ITERS, TOL, hist_cap=MAX_ITERS)
+    assert st == 0
+    check_counts(it, ref)
+    check_true_residual(a, B, X)
+    check_history("randdd", hist, ref)
+
+
+def test_rectangular_rejected(mspmv):
+    ro = np.arange(0, 11, dtype=np.int32)
+    a = mspmv.CsrMatrix.from_arrays(12, ro, np.arange(10, dtype=np.int32), np.ones(10))
+    with mspmv.GpuCsr(a, device=0) as g:
+        with pytest.raises(mspmv.MspmvError) as ei:
+            g.bicgstab(np.ones((10, 2)), 10, TOL)
+        assert ei.value.status == 1
+        with pytest.raises(mspmv.MspmvError):
+            g.bicgstab(np.ones((10, 2)), -1, TOL)
+
+
+def test_device_pointers(mspmv):
+    """mspmv_dbicgstab_multi_dev on device panels is the host-pointer solve; a panel that is not 16-byte
+    aligned is rejected."""
+    a = tb.matrix("randdd")
+    B = tb.rhs(777, 2)
+    with mspmv.GpuCsr(csr(mspmv, a), device=0) as g:
+        X, it, hist, st = g.bicgstab(B, MAX_ITERS, TOL, hist_cap=MAX_ITERS)
+        dB, dX = mspmv.DeviceBuffer.from_array(B), mspmv.DeviceBuffer(8 * B.size + 16)
+        it_d, hist_d, st_d = g.bicgstab_dev(dB, dX, 2, MAX_ITERS, TOL, hist_cap=MAX_ITERS)
+        Xd = dX.download(B.shape)
+
+        class Shifted:
+            ptr = dX.ptr + 8
+
+        with pytest.raises(mspmv.MspmvError) as ei:
+            g.bicgstab_dev(dB, Shifted, 2, MAX_ITERS, TOL)
+        assert ei.value.status == 1
+        dB.free()
+        dX.free()
+    assert st == 0 and st_d == 0 and it_d == it
+    np.testing.assert_array_equal(Xd, X)
+    np.testing.assert_array_equal(hist_d, hist)
+
+
+def test_facade_and_cli(mspmv, orc, tmp_path):
+    """BiCGStabSolveMultiple and `mspmv_cg --solver=bicgstab --multi` run the binding's solve: same
+    right-hand side (srand(42) over the flat panel), same threshold (tol x the norm of the panel's first n
+    entries, the driver's rule), same iteration count."""
+    a = tb.matrix("convdiff30")
+    ro, ci, va = a
+    n, L, tol = len(ro) - 1, 4, 1e-9
+    p = tmp_path / "convdiff.mtx"
+    with open(p, "w") as f:
+        f.write("%%MatrixMarket matrix coordinate real general\n")
+        f.write(f"{n} {n} {len(ci)}\n")
+        rows = np.repeat(np.arange(n), np.diff(ro))
+        for r, c, v in zip(rows, ci, va):
+            f.write(f"{r + 1} {c + 1} {float(v)!r}\n")
+    flat = orc.glibc_rand(42, n * L)
+    threshold = float(np.sqrt(np.sum(flat[:n] ** 2)) * tol)
+    m = csr(mspmv, a)
+    with mspmv.GpuCsr(m, device=0) as g:
+        Xb, it_b, _, st = g.bicgstab(flat.reshape(n, L), 50000, threshold)
+    assert st == 0 and it_b > 10
+    Xf = np.zeros(n * L)
+    errs = []
+    it_f = mspmv.BiCGStabSolveMultiple(m, flat, Xf, L, 50000, threshold, max_errors=errs)
+    assert it_f == it_b and len(errs) == it_f
+    np.testing.assert_array_equal(Xf.reshape(n, L), Xb)
+    out = tmp_path / "e.csv"
+    r = subprocess.run([os.path.join(BIN, "mspmv_cg"), f"--mtx={p}", "--solver=bicgstab", "--multi", "--num_vectors=4",
+                        f"--tolerance={tol!r}", f"--output={out}", "--quiet"], capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 0 and "Min time" in r.stdout, r.stdout + r.stderr
+    it_cli = float(r.stdout.split("Iters:")[1].split(",")[0])
+    assert it_cli == it_b, (r.stdout, it_b)
+    lines = open(out).read().strip().splitlines()
+    assert lines[0] == "iteration,max_error" and len(lines) == 1 + it_b
