@@ -126,6 +126,20 @@ MSPMV_API mspmv_status mspmv_dspmv_dev(mspmv_handle h, const double *d_x, double
  * columns.  Even-L panels must be 16-byte aligned. */
 MSPMV_API mspmv_status mspmv_dspmm(mspmv_handle h, const double *X, double *Y, int L);
 MSPMV_API mspmv_status mspmv_dspmm_dev(mspmv_handle h, const double *d_X, double *d_Y, int L);
+/* Batched product: d_Y[i] = A_i d_X[i] for `count` handles on one device, L in {1, 2, 4, 8, 16} (panels
+ * 16-byte aligned for L > 1).  Product i is enqueued on hs[i]'s own stream by the launch path of
+ * mspmv_dspmm_dev (same kernel, plan and order of sums) and the call returns without a host sync, with no
+ * events and no waits between streams: work issued earlier on handle i precedes its product, work issued
+ * later follows it, and products of different handles are unordered and may run at the same time.  A handle
+ * listed twice is legal; its products run in order.  So that no overlap is a race, the y ranges
+ * [d_Y[i], +8 m_i L) must be pairwise disjoint and disjoint from every x range [d_X[j], +8 n_j L), j = i
+ * included (a shared x is fine): otherwise MSPMV_ERR_INVALID, naming the two products, and nothing is
+ * launched.  No reference counterpart. */
+MSPMV_API mspmv_status mspmv_spmm_batch_dev(int count, const mspmv_handle *hs, const double *const *d_X,
+                                            double *const *d_Y, int L);
+/* Block until every listed handle's stream has drained and run mspmv_check_faults on each (all of them,
+ * even after one reports): MSPMV_ERR_FAULT, naming the first such product, if a ticket fault was raised. */
+MSPMV_API mspmv_status mspmv_sync_batch(int count, const mspmv_handle *hs);
 
 /* ---- CG ----------------------------------------------------------------------------- */
 /* Single-RHS CG, CGSolveSingle (work_2025/main/single_strategy.hpp:102-170): x0 = 0,
@@ -252,11 +266,16 @@ MSPMV_API mspmv_status mspmv_dpcg_ic0_multi_dev(mspmv_handle a, mspmv_ic0 m, con
 MSPMV_API mspmv_status mspmv_time_spmm_dev(mspmv_handle h, const double *d_X, double *d_Y, int L, int reps,
                                  size_t flush_bytes, double *avg_ms);
 /* Batch form for benchmarks: `reps` steps, each step one SpMM launch per handle (all handles
- * on one device), every launch enqueued back to back on hs[0]'s stream, HIP events only
- * around the whole region.  *step_ms = average event time per step; *tile_kernel_ms =
- * average duration of one merge tile kernel launch: region time / launches when a step holds
- * only tile kernels (the launch boundary included), else from a second pass that brackets
- * every tile launch with events; *kernels_per_step = launches per step (tile + fix-up). */
+ * on one device), HIP events only around the whole region.  Product i of every step is enqueued
+ * on hs[i]'s own stream, as mspmv_spmm_batch_dev enqueues it, so the launches of a step may run
+ * at the same time (the y / x ranges must then be disjoint, as there); the start event is
+ * recorded on hs[0]'s stream and waited on once by every other stream, and the end event follows
+ * one done event per other stream: nothing per step.  MSPMV_BATCH_OVERLAP=0 (read per call):
+ * every launch back to back on hs[0]'s stream instead; a batch of one handle is that form.
+ * *step_ms = region time / reps; *tile_kernel_ms = region time / (reps x count): the region
+ * time per product -- the duration of one launch (its boundary included) in the single-stream
+ * form, less than that when the launches of a step overlap; *kernels_per_step = launches per
+ * step (one per handle with rows). */
 MSPMV_API mspmv_status mspmv_time_spmm_batch_dev(int count, const mspmv_handle *hs, const double *const *d_X,
                                                  double *const *d_Y, int L, int reps, double *step_ms,
                                                  double *tile_kernel_ms, int *kernels_per_step);
@@ -358,7 +377,10 @@ MSPMV_API mspmv_status mspmv_check_faults(mspmv_handle h);
  * iteration (MSPMV_POISON_FILL), optionally zeroes them again after the first iteration is enqueued
  * (MSPMV_POISON_LATE_ZERO: the ordering of round 5's unordered null-stream memset) and optionally
  * records the fault without stopping (MSPMV_POISON_NO_STOP: the solve runs to its stop test and then
- * returns MSPMV_ERR_FAULT with the iteration count it reached).  One solve only. */
+ * returns MSPMV_ERR_FAULT with the iteration count it reached).  One solve only.  A pending
+ * MSPMV_POISON_FILL is also taken by h's next product in mspmv_spmm_batch_dev when its plan splits rows
+ * between tiles: that product starts from split-row tickets of `value` (zeroed again behind it) and
+ * mspmv_sync_batch reports it. */
 enum { MSPMV_POISON_FILL = 1, MSPMV_POISON_LATE_ZERO = 2, MSPMV_POISON_NO_STOP = 4 };
 MSPMV_API mspmv_status mspmv_test_poison_tickets(mspmv_handle h, unsigned value, int flags);
 

@@ -2515,44 +2515,117 @@ mspmv_status mspmv_time_spmm_dev(mspmv_handle h, const double *d_X, double *d_Y,
     return MSPMV_OK;
 }
 
-mspmv_status mspmv_time_spmm_batch_dev(int count, const mspmv_handle *hs, const double *const *d_X,
-                                       double *const *d_Y, int L, int reps, double *step_ms, double *tile_kernel_ms,
-                                       int *kernels_per_step)
+}  // extern "C"
+
+// ---- batched products: one product per handle, each on its handle's own stream ----------------
+// Independent products on distinct streams may run at the same time, so a y that another product of the
+// batch reads or writes would be a race: every y range [d_Y[i], +8 m_i L) must be disjoint from every other
+// y range and from every x range [d_X[j], +8 n_j L), j = i included (x of a 0-row matrix is never read).
+// A shared x is fine.
+static mspmv_status batch_check_ranges(const char *who, int count, const mspmv_handle *hs, const double *const *d_X,
+                                       double *const *d_Y, int L)
+{
+    auto hit = [](uintptr_t a, size_t na, uintptr_t b, size_t nb) { return na && nb && a < b + nb && b < a + na; };
+    for (int i = 0; i < count; ++i) {
+        const uintptr_t y = (uintptr_t)d_Y[i];
+        const size_t ny = sizeof(double) * (size_t)hs[i]->m * L;
+        for (int j = 0; j < count; ++j) {
+            if (j > i && hit(y, ny, (uintptr_t)d_Y[j], sizeof(double) * (size_t)hs[j]->m * L))
+                return invalid(std::string(who) + ": products " + std::to_string(i) + " and " + std::to_string(j) +
+                               " write overlapping y ranges");
+            if (hs[j]->m > 0 && hit(y, ny, (uintptr_t)d_X[j], sizeof(double) * (size_t)hs[j]->n * L))
+                return invalid(std::string(who) + ": y of product " + std::to_string(i) + " overlaps x of product " +
+                               std::to_string(j));
+        }
+    }
+    return MSPMV_OK;
+}
+
+// The checks the batch entries share (same device, non-null vectors of non-empty products, 16-byte panels
+// for L > 1) and each handle's plain plan for width L; *kps = products that launch a kernel.
+static mspmv_status batch_plans(const char *who, int count, const mspmv_handle *hs, const double *const *d_X,
+                                double *const *d_Y, int L, std::vector<const TilePlan *> &plans, int *kps)
+{
+    for (int i = 0; i < count; ++i) {
+        ST_TRY(check_handle(hs[i]));
+        if (hs[i]->device != hs[0]->device)
+            return invalid(std::string(who) + ": batch handles must share a device (products 0 and " +
+                           std::to_string(i) + ")");
+        if (hs[i]->m > 0 && (!d_X[i] || !d_Y[i]))
+            return invalid(std::string(who) + ": null vector");
+        if (L > 1 && (!aligned16(d_X[i]) || !aligned16(d_Y[i])))
+            return invalid("multi-vector panels must be 16-byte aligned");
+    }
+    ST_TRY(check_handle(hs[0]));
+    plans.assign((size_t)count, nullptr);
+    *kps = 0;
+    for (int i = 0; i < count; ++i) {
+        if (hs[i]->m == 0)  // no rows: no plan, no launch (as mspmv_dspmm_dev)
+            continue;
+        ST_TRY(get_plan(hs[i], L, &plans[(size_t)i], true));
+        *kps += plans[(size_t)i]->num_tiles ? 1 : 0;
+    }
+    return MSPMV_OK;
+}
+
+// MSPMV_BATCH_OVERLAP, read per call (one process can alternate the two forms of the timing entry):
+// 0 = every launch of a step on hs[0]'s stream, back to back; otherwise product i on hs[i]'s own stream.
+static bool batch_overlap_env()
+{
+    const char *v = getenv("MSPMV_BATCH_OVERLAP");
+    return !(v && v[0] == '0');
+}
+
+mspmv_status mspmv::time_spmm_batch(int count, const mspmv_handle *hs, const double *const *d_X, double *const *d_Y,
+                                    int L, int reps, double *step_ms, double *tile_kernel_ms, int *kernels_per_step,
+                                    bool overlap)
 {
     if (count < 1 || !hs || !d_X || !d_Y || reps < 1 || !step_ms)
         return invalid("bad batch timing arguments");
     if (!supported_L(L))
         return (set_error("L must be one of 1, 2, 4, 8, 16"), MSPMV_ERR_UNSUPPORTED);
-    for (int i = 0; i < count; ++i) {
-        ST_TRY(check_handle(hs[i]));
-        if (hs[i]->device != hs[0]->device)
-            return invalid("batch handles must share a device");
-        if (L > 1 && (!aligned16(d_X[i]) || !aligned16(d_Y[i])))
-            return invalid("multi-vector panels must be 16-byte aligned");
-    }
-    ST_TRY(check_handle(hs[0]));
-    std::vector<const TilePlan *> plans(count);
+    std::vector<const TilePlan *> plans;
     int kps = 0;
-    for (int i = 0; i < count; ++i) {
-        ST_TRY(get_plan(hs[i], L, &plans[i], true));
-        kps += plans[i]->num_tiles ? 1 : 0;
-    }
+    ST_TRY(batch_plans("time_spmm_batch", count, hs, d_X, d_Y, L, plans, &kps));
     hipStream_t s = hs[0]->stream;
-    for (int i = 0; i < count; ++i)  // everything after this point is ordered on hs[0]'s stream
+    // the other streams of the overlapped form (handles may share one: a CU-masked stream, a handle listed twice)
+    std::vector<hipStream_t> others;
+    for (int i = 1; i < count && overlap; ++i)
+        if (hs[i]->stream != s && std::find(others.begin(), others.end(), hs[i]->stream) == others.end())
+            others.push_back(hs[i]->stream);
+    if (!others.empty())  // launches of one step may run together
+        ST_TRY(batch_check_ranges("time_spmm_batch", count, hs, d_X, d_Y, L));
+    for (int i = 0; i < count; ++i)  // everything after this point is ordered by the region's events
         HIP_TRY(hipStreamSynchronize(hs[i]->stream));
-    // The timed steps: launches back to back, events only around the whole region (one kernel per
-    // product: split rows are closed inside the tile kernel).
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    for (auto &x : ev)
-        HIP_TRY(hipEventCreate(&x));
-    hipError_t e = hipEventRecord(ev[0], s);
+    // The timed steps: events only around the whole region (one kernel per product: split rows are closed
+    // inside the tile kernel).  Single-stream form: every launch back to back on hs[0]'s stream.  Overlapped
+    // form: product i on hs[i]'s own stream; the start event, on hs[0]'s stream, is waited on by every other
+    // stream once, and each of those records one done event at the end that hs[0]'s stream waits on before
+    // the end event -- 2 + one event per extra stream per region, nothing per step (an event per launch
+    // costs 5-10 us, more than the fill and drain the overlap hides).
+    std::vector<hipEvent_t> ev(2 + others.size(), nullptr);
+    hipError_t e = hipSuccess;
+    for (size_t k = 0; k < ev.size() && e == hipSuccess; ++k)
+        e = k < 2 ? hipEventCreate(&ev[k]) : hipEventCreateWithFlags(&ev[k], hipEventDisableTiming);
+    if (e == hipSuccess)
+        e = hipEventRecord(ev[0], s);
+    for (size_t k = 0; k < others.size() && e == hipSuccess; ++k)
+        e = hipStreamWaitEvent(others[k], ev[0], 0);
     for (int r = 0; r < reps && e == hipSuccess; ++r)
         for (int i = 0; i < count && e == hipSuccess; ++i) {
+            if (!plans[(size_t)i])
+                continue;
             hipStream_t own = hs[i]->stream;
-            hs[i]->stream = s;
-            e = launch_spmm_tile_only(hs[i], *plans[i], d_X[i], d_Y[i], L);
+            if (!overlap)
+                hs[i]->stream = s;
+            e = launch_spmm_tile_only(hs[i], *plans[(size_t)i], d_X[i], d_Y[i], L);
             hs[i]->stream = own;
         }
+    for (size_t k = 0; k < others.size() && e == hipSuccess; ++k) {
+        e = hipEventRecord(ev[2 + k], others[k]);
+        if (e == hipSuccess)
+            e = hipStreamWaitEvent(s, ev[2 + k], 0);
+    }
     if (e == hipSuccess)
         e = hipEventRecord(ev[1], s);
     if (e == hipSuccess)
@@ -2562,7 +2635,8 @@ mspmv_status mspmv_time_spmm_batch_dev(int count, const mspmv_handle *hs, const 
         e = hipEventElapsedTime(&total, ev[0], ev[1]);
     const double sum = (double)total;
     for (auto &x : ev)
-        (void)hipEventDestroy(x);
+        if (x)
+            (void)hipEventDestroy(x);
     if (e != hipSuccess) {
         set_error(std::string("batch timing: ") + hipGetErrorString(e));
         return MSPMV_ERR_HIP;
@@ -2573,6 +2647,68 @@ mspmv_status mspmv_time_spmm_batch_dev(int count, const mspmv_handle *hs, const 
     if (kernels_per_step)
         *kernels_per_step = kps;
     return MSPMV_OK;
+}
+
+extern "C" {
+
+mspmv_status mspmv_time_spmm_batch_dev(int count, const mspmv_handle *hs, const double *const *d_X,
+                                       double *const *d_Y, int L, int reps, double *step_ms, double *tile_kernel_ms,
+                                       int *kernels_per_step)
+{
+    return mspmv::time_spmm_batch(count, hs, d_X, d_Y, L, reps, step_ms, tile_kernel_ms, kernels_per_step,
+                                  batch_overlap_env());
+}
+
+mspmv_status mspmv_spmm_batch_dev(int count, const mspmv_handle *hs, const double *const *d_X, double *const *d_Y,
+                                  int L)
+{
+    if (count < 1 || !hs || !d_X || !d_Y)
+        return invalid("spmm_batch: count >= 1 and non-null arrays required");
+    if (!supported_L(L))
+        return invalid("spmm_batch: L must be one of 1, 2, 4, 8, 16");
+    std::vector<const TilePlan *> plans;
+    int kps = 0;
+    ST_TRY(batch_plans("spmm_batch", count, hs, d_X, d_Y, L, plans, &kps));
+    ST_TRY(batch_check_ranges("spmm_batch", count, hs, d_X, d_Y, L));
+    // Product i on hs[i]'s own stream, by the launch path of a single product: no events, no waits between
+    // streams, no host sync.  Stream order on each handle is all the ordering there is.
+    for (int i = 0; i < count; ++i) {
+        mspmv_handle_s *h = hs[i];
+        if (!plans[(size_t)i])
+            continue;
+        const TilePlan &plan = *plans[(size_t)i];
+        // test hook (mspmv_test_poison_tickets): this product meets dirty split-row tickets, as an unordered
+        // zeroing leaves them; zeroed again behind it, so the handle's next product is clean
+        const bool poison = (h->poison_flags & MSPMV_POISON_FILL) && plan.num_carries && plan.d_fix_cnt;
+        if (poison) {
+            h->poison_flags = 0;
+            HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)plan.d_fix_cnt, (int)h->poison_value, (size_t)plan.num_tiles,
+                                      h->stream));
+        }
+        HIP_TRY(launch_spmm_tile_only(h, plan, d_X[i], d_Y[i], L));
+        if (poison)
+            HIP_TRY(hipMemsetAsync(plan.d_fix_cnt, 0, sizeof(unsigned) * (size_t)plan.num_tiles, h->stream));
+    }
+    return MSPMV_OK;
+}
+
+mspmv_status mspmv_sync_batch(int count, const mspmv_handle *hs)
+{
+    if (count < 1 || !hs)
+        return invalid("sync_batch: count >= 1 and handles required");
+    // every stream drained and every fault word read (and cleared) even when an earlier handle reports
+    mspmv_status st = MSPMV_OK;
+    std::string msg;
+    for (int i = 0; i < count; ++i) {
+        const mspmv_status si = mspmv_check_faults(hs[i]);
+        if (si != MSPMV_OK && st == MSPMV_OK) {
+            st = si;
+            msg = "product " + std::to_string(i) + ": " + mspmv_last_error();
+        }
+    }
+    if (st != MSPMV_OK)
+        set_error(msg);
+    return st;
 }
 
 mspmv_status mspmv_last_kernel_ms(mspmv_handle h, double *tile_kernel_ms, int *kernels_per_call)

@@ -628,7 +628,7 @@ mspmv_status mspmv_dist_time_local_dev(mspmv_dist d, double *d_Y_own, int L, int
         }
     double kern = 0.0;
     int kps = 0;
-    return mspmv_time_spmm_batch_dev(n, hs, xs, ys, L, reps, avg_ms, &kern, &kps);
+    return mspmv::time_spmm_batch(n, hs, xs, ys, L, reps, avg_ms, &kern, &kps, false);
 }
 
 mspmv_status mspmv_dist_spmm_dev(mspmv_dist d, const double *d_X_own, double *d_Y_own, int L)

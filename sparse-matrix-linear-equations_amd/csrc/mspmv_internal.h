@@ -626,6 +626,10 @@ mspmv_status csr_create_on_stream(const mspmv_csr_d *host, int device, hipStream
 // parent's row offsets on the host.
 mspmv_status csr_create_view(mspmv_handle parent, int row_lo, int row_hi, const int *host_row_offsets,
                              mspmv_handle *out);
+// mspmv_time_spmm_batch_dev's body.  overlap: product i of every step on hs[i]'s own stream (the region's
+// events tie the streams together once); false: every launch back to back on hs[0]'s stream.
+mspmv_status time_spmm_batch(int count, const mspmv_handle *hs, const double *const *d_X, double *const *d_Y, int L,
+                             int reps, double *step_ms, double *tile_kernel_ms, int *kernels_per_step, bool overlap);
 // SPAI-preconditioned block CG (SPAISolveMultiple, work_2025/main/sparse_approximate_inverse.hpp:
 // 30-230) on A's handle h with the preconditioner's handle hm (same shape and device): init
 // (X = 0, R = B, Z = M R, P = Z, rs_old = R.Z) and one iteration (AP = A P -> alpha; X, R update

@@ -93,6 +93,8 @@ _SIGS = {
     "mspmv_dspmv_dev": (_I, [_P, _P, _P]),
     "mspmv_dspmm": (_I, [_P, _P, _P, _I]),
     "mspmv_dspmm_dev": (_I, [_P, _P, _P, _I]),
+    "mspmv_spmm_batch_dev": (_I, [_I, ctypes.POINTER(_P), ctypes.POINTER(_P), ctypes.POINTER(_P), _I]),
+    "mspmv_sync_batch": (_I, [_I, ctypes.POINTER(_P)]),
     "mspmv_dcg_single": (_I, [_P, _P, _P, _I, _D, _PI, _P, _I]),
     "mspmv_dcg_single_dev": (_I, [_P, _P, _P, _I, _D, _PI, _P, _I]),
     "mspmv_cg_resident_stamps": (_I, [_P, _P, _P, _I, _D, _PI, _P, _I, _PI]),
@@ -487,7 +489,8 @@ class GpuCsr:
         _check(lib.mspmv_check_faults(self.h), "check_faults")
 
     def test_poison_tickets(self, value: int, flags: int = POISON_FILL):
-        """Test hook: the next CG solve's fold tickets start at `value` (mspmv_test_poison_tickets)."""
+        """Test hook: the next CG solve's fold tickets start at `value` (mspmv_test_poison_tickets); so do the
+        split-row tickets of the handle's next product in spmm_batch_dev."""
         _check(lib.mspmv_test_poison_tickets(self.h, value, flags), "test_poison_tickets")
 
     def set_cu_limit(self, num_cus: int):
@@ -740,13 +743,35 @@ def spai_values(a: CsrMatrix) -> np.ndarray:
     return out[: a.num_nonzeros]
 
 
-def time_spmm_batch(gs, dXs, dYs, L: int, reps: int):
-    """Time `reps` steps of one SpMM launch per matrix, all on gs[0]'s stream.
-    Returns (ms per step, ms per merge-tile kernel launch, kernels per step)."""
+def _batch_args(gs, dXs=None, dYs=None):
     n = len(gs)
     H = (_P * n)(*[g.h for g in gs])
-    X = (_P * n)(*[b.ptr for b in dXs])
-    Y = (_P * n)(*[b.ptr for b in dYs])
+    X = (_P * n)(*[b.ptr for b in dXs]) if dXs is not None else None
+    Y = (_P * n)(*[b.ptr for b in dYs]) if dYs is not None else None
+    return n, H, X, Y
+
+
+def spmm_batch_dev(gs, dXs, dYs, L: int = 1, sync: bool = True):
+    """mspmv_spmm_batch_dev: dYs[i] = A_i dXs[i], product i on gs[i]'s own stream (products of different
+    handles unordered, so they may overlap; y ranges disjoint from each other and from every x range).
+    Complete only after a sync -- sync_batch here unless sync=False."""
+    n, H, X, Y = _batch_args(gs, dXs, dYs)
+    _check(lib.mspmv_spmm_batch_dev(n, H, X, Y, L), "spmm_batch_dev")
+    if sync:
+        sync_batch(gs)
+
+
+def sync_batch(gs):
+    """mspmv_sync_batch: drain every handle's stream; raises MspmvError(FAULT) if a product raised a ticket
+    fault since the handle's last check."""
+    n, H, _, _ = _batch_args(gs)
+    _check(lib.mspmv_sync_batch(n, H), "sync_batch")
+
+
+def time_spmm_batch(gs, dXs, dYs, L: int, reps: int):
+    """Time `reps` steps of one SpMM launch per matrix, product i on gs[i]'s stream (MSPMV_BATCH_OVERLAP=0:
+    all on gs[0]'s).  Returns (ms per step, region ms per product, kernels per step)."""
+    n, H, X, Y = _batch_args(gs, dXs, dYs)
     step, kern, kps = ctypes.c_double(), ctypes.c_double(), ctypes.c_int()
     _check(lib.mspmv_time_spmm_batch_dev(n, H, X, Y, L, reps, ctypes.byref(step), ctypes.byref(kern),
                                          ctypes.byref(kps)), "time_spmm_batch")

@@ -59,6 +59,22 @@ def frac(nbytes, us):
     return nbytes / (us * 1e-6) / 1e9 / PEAK
 
 
+def region_per_launch(trace, kernel, grid, launches, norm=lambda k: k):
+    """A batch leg's timed region in the trace: the last `launches` dispatches of (kernel, grid), (last end -
+    first start) / launches in us, and how many were found.  The batch's launches run on their handles' own
+    streams and may overlap, so each lasts longer than its share of the region: bench's per-product time
+    (region / launches) is compared with this, not with the average kernel duration."""
+    recs = [r for r in csv.DictReader(open(trace)) if r.get("Kind", "KERNEL_DISPATCH") == "KERNEL_DISPATCH"]
+    recs = [r for r in recs if norm(short_name(r["Kernel_Name"])) == norm(kernel)
+            and int(r["Grid_Size_X"]) * int(r["Grid_Size_Y"]) * int(r["Grid_Size_Z"]) == grid]
+    recs.sort(key=lambda r: int(r["Dispatch_Id"]))
+    recs = recs[-launches:] if launches > 0 else recs
+    if not recs:
+        return 0.0, 0
+    span = max(int(r["End_Timestamp"]) for r in recs) - min(int(r["Start_Timestamp"]) for r in recs)
+    return span / 1000.0 / len(recs), len(recs)
+
+
 def cg_loop_times(trace, iterations):
     """Kernel-busy time per iteration over both solves (warm + timed: same inputs, same iteration
     count), counting kernels launched at least once per iteration, and the timed solve's span (first
@@ -104,10 +120,14 @@ def main(src, dst):
         rf = prof_bench["roofline"]
         norm = lambda k: k.replace(",256>", ">").replace(",6,false>", ",6>")  # noqa: E731  default template arguments
         kr = max((r for r in rows if norm(r["kernel"]) == norm(rf["kernel"])), key=lambda r: r["grid"])
+        # a batch leg: the timed region (the last steps x batch launches) per launch
+        per, found = region_per_launch(tr, kr["kernel"], kr["grid"],
+                                       prof_bench["steps"] * prof_bench["config"]["batch"])
         lines.append(f"| headline {rf['kernel']} | frac {bench['roofline']['frac'] if bench else '-'} "
                      f"(kernel_ms {bench['roofline']['kernel_ms'] if bench else '-'}) | frac "
-                     f"{frac(rf['bytes_per_launch'], kr['avg_us']):.4f} (avg {kr['avg_us']} us, median "
-                     f"{kr['median_us']} us) | {kr['kernel']} grid {kr['grid']} x{kr['calls']} |")
+                     f"{frac(rf['bytes_per_launch'], per):.4f} (region / launches {per:.3f} us over the last {found}; "
+                     f"one launch alone: avg {kr['avg_us']} us, median {kr['median_us']} us) | "
+                     f"{kr['kernel']} grid {kr['grid']} x{kr['calls']} |")
         if os.path.isdir(os.path.join(src, "pmc_fetch")):
             pmc_traffic.main(["", src, out("pmc_traffic.json")])
 
@@ -140,9 +160,12 @@ def main(src, dst):
         if leg == "pwtk_perturbed":
             norm = lambda k: k.replace(",6,false>", ",6>")  # noqa: E731
             kr = max((r for r in rows if norm(r["kernel"]) == norm(lj["kernel"])), key=lambda r: r["calls"])
+            # a batch leg (bench.run_pwtk_perturbed: 4 matrices, 50 timed steps after 5 warm-up ones)
+            per, found = region_per_launch(tr, kr["kernel"], kr["grid"], 4 * 50)
             lines.append(f"| {leg} {lj['kernel']} | frac {lj['frac']} (kernel_ms {lj['kernel_ms']}) | frac "
-                         f"{frac(lj['bytes_per_launch'], kr['avg_us']):.4f} (avg {kr['avg_us']} us, median "
-                         f"{kr['median_us']} us) | {kr['kernel']} grid {kr['grid']} x{kr['calls']} |")
+                         f"{frac(lj['bytes_per_launch'], per):.4f} (region / launches {per:.3f} us over the last {found}; "
+                         f"one launch alone: avg {kr['avg_us']} us, median {kr['median_us']} us) | "
+                         f"{kr['kernel']} grid {kr['grid']} x{kr['calls']} |")
         elif leg in ("spmm16", "spmv_shapes"):
             L = 16 if leg == "spmm16" else 1
             shapes = [k for k in (("cant", "pwtk") if leg == "spmm16" else ("cant", "rma10", "powerlaw")) if k in lj]
