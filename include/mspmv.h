@@ -231,7 +231,11 @@ MSPMV_API mspmv_status mspmv_dpcg_spai_multi_dev(mspmv_handle a, mspmv_handle m,
  * reference: L has A's lower-triangle pattern (diagonal included, A's CSR order); on a
  * non-positive pivot the factorization restarts with the diagonal shifted by 1e-3, x10 per
  * attempt, 20 attempts (MSPMV_ERR_BREAKDOWN after that).  mspmv_ic0_nnz gives L's nonzero count;
- * l_row_offsets[n+1], l_cols / l_vals[nnz_l] receive L; *shift (nullable) the shift used. */
+ * l_row_offsets[n+1], l_cols / l_vals[nnz_l] receive L; *shift (nullable) the shift used.
+ * Precondition, checked by mspmv_ic0_factor: in every row of A the entries with column <= row
+ * are strictly ascending and end in the diagonal (sorted columns, no duplicates, every diagonal
+ * present) -- the recurrence merges rows in that order and takes a row's last lower entry as its
+ * diagonal.  Anything else is MSPMV_ERR_INVALID, the message naming the first such row. */
 MSPMV_API mspmv_status mspmv_ic0_nnz(const mspmv_csr_d *a, int *nnz_l);
 MSPMV_API mspmv_status mspmv_ic0_factor(const mspmv_csr_d *a, int *l_row_offsets, int *l_cols, double *l_vals,
                                         double *shift);
@@ -244,7 +248,8 @@ MSPMV_API mspmv_status mspmv_csr_transpose(const mspmv_csr_d *in, int *out_row_o
 MSPMV_API mspmv_status mspmv_ic0_create(const mspmv_csr_d *l, int device, mspmv_ic0 *out);
 MSPMV_API mspmv_status mspmv_ic0_destroy(mspmv_ic0 m);
 /* PCGSolveMultiple (work_2025/main/incomplete_cholesky.hpp:33-199) on the GPU: Z = L^-T L^-1 R by
- * two sync-free triangular solves per application (one wave per row, per-row ready flags),
+ * two sync-free triangular solves per application (one wave per row in dependency-level order;
+ * the output panel starts filled with a pending pattern and a consumer polls the value it needs),
  * merge-path SpMM for A P, the reference's masks and max-residual history.  A stalled solve
  * (a dependency never ready) stops the iteration and is reported as MSPMV_ERR_STALL, never a
  * hang.  mspmv_ic0_create rejects a factor with an entry above the diagonal or a row without
@@ -255,6 +260,14 @@ MSPMV_API mspmv_status mspmv_dpcg_ic0_multi(mspmv_handle a, mspmv_ic0 m, const d
 MSPMV_API mspmv_status mspmv_dpcg_ic0_multi_dev(mspmv_handle a, mspmv_ic0 m, const double *d_B, double *d_X, int L,
                                                 int max_iters, double tolerance, mspmv_spmm_kernel kernel,
                                                 int *iters, double *max_err_hist, int hist_cap);
+/* One triangular solve with the factor: transpose = 0 solves L X = B, 1 solves L^T X = B.
+ * Device panels n x L row-major, 16-byte aligned, L in {1,2,4,8,16}; B and X must not overlap
+ * (X is pre-filled with the pending pattern).  Runs on a's stream with a's control block,
+ * synchronises; MSPMV_ERR_STALL exactly as the PCG reports it.  MSPMV_ERR_INVALID (X untouched)
+ * for a factor of another shape or device, a null or misaligned panel, overlapping panels;
+ * MSPMV_ERR_UNSUPPORTED for another L. */
+MSPMV_API mspmv_status mspmv_ic0_solve_dev(mspmv_handle a, mspmv_ic0 m, int transpose, const double *d_B,
+                                           double *d_X, int L);
 
 /* ---- measurement helpers (HIP events on the handle's stream) ------------------------ */
 /* Enqueue `reps` back-to-back SpMV (L == 1) or SpMM launches on device buffers and return

@@ -2331,8 +2331,6 @@ mspmv_status mspmv_ic0_create(const mspmv_csr_d *l, int device, mspmv_ic0 *out)
     up(&m->d_uva, uva.data(), (size_t)nnz);
     up(&m->d_fwd_order, fwd_order.data(), (size_t)n);
     up(&m->d_bwd_order, bwd_order.data(), (size_t)n);
-    if (st == MSPMV_OK)
-        st = dev_alloc(&m->d_ready, (size_t)std::max(n, 1));
     if (st != MSPMV_OK) {
         mspmv_ic0_destroy(m);
         return st;
@@ -2354,7 +2352,6 @@ mspmv_status mspmv_ic0_destroy(mspmv_ic0 m)
     dev_free(m->d_uva);
     dev_free(m->d_fwd_order);
     dev_free(m->d_bwd_order);
-    dev_free(m->d_ready);
     if (m->d_y)
         (void)hipFree(m->d_y);
     delete m;
@@ -2380,6 +2377,42 @@ mspmv_status mspmv_dpcg_ic0_multi(mspmv_handle a, mspmv_ic0 m, const double *B, 
     if (!m)
         return invalid("null IC(0) factor");
     return cg_solve_host(a, B, X, L, max_iters, tolerance, iters, max_err_hist, hist_cap, nullptr, m);
+}
+
+// One triangular solve with the factor, alone: the pass the PCG's preconditioner apply runs twice
+// (launch_ic0_trsv), on a's stream with a's control word, synchronised.
+mspmv_status mspmv_ic0_solve_dev(mspmv_handle a, mspmv_ic0 m, int transpose, const double *d_B, double *d_X, int L)
+{
+    ST_TRY(check_handle(a));
+    if (!m)
+        return invalid("null IC(0) factor");
+    if (transpose != 0 && transpose != 1)
+        return invalid("transpose must be 0 (L X = B) or 1 (L^T X = B)");
+    if (a->m != a->n || m->n != a->m || m->device != a->device)
+        return invalid("the IC(0) factor must match the matrix's shape and device");
+    if (!supported_L(L))
+        return (set_error("L must be one of 1, 2, 4, 8, 16"), MSPMV_ERR_UNSUPPORTED);
+    if (m->n == 0)
+        return MSPMV_OK;
+    if (!d_B || !d_X)
+        return invalid("null panel");
+    if (!aligned16(d_B) || !aligned16(d_X))
+        return invalid("triangular-solve panels must be 16-byte aligned");
+    const uintptr_t b0 = (uintptr_t)d_B, x0 = (uintptr_t)d_X, bytes = sizeof(double) * (size_t)m->n * L;
+    if (b0 < x0 + bytes && x0 < b0 + bytes)
+        return invalid("triangular-solve panels must not overlap (X is pre-filled with the pending pattern)");
+    if (!a->d_ctrl)
+        ST_TRY(dev_alloc(&a->d_ctrl, 1));
+    HIP_TRY(hipMemsetAsync(a->d_ctrl, 0, sizeof(CgControl), a->stream));
+    HIP_TRY(launch_ic0_trsv(m, transpose == 0, d_B, d_X, L, a->d_ctrl, a->stream));
+    HIP_TRY(hipStreamSynchronize(a->stream));
+    CgControl fin{};
+    HIP_TRY(hipMemcpy(&fin, a->d_ctrl, sizeof(CgControl), hipMemcpyDeviceToHost));
+    if (fin.breakdown == 2) {
+        set_error("IC(0) solve: a triangular-solve dependency never became ready (solve stalled)");
+        return MSPMV_ERR_STALL;
+    }
+    return MSPMV_OK;
 }
 
 // ---- measurement ---------------------------------------------------------------------------

@@ -1092,28 +1092,29 @@ static void trsv_L(const mspmv_ic0_s *ic, bool fwd, const double *b, double *x, 
                            ic->d_bwd_order, b, x, ctrl);
 }
 
-// Z = L^-T (L^-1 R): ForwardSolveMultiple into ic->d_y, then BackwardSolveMultiple
-// (incomplete_cholesky.hpp:89-92, :166-167); the ready flags are cleared before each solve.
-static hipError_t ic0_apply(mspmv_handle_s *h, mspmv_ic0_s *ic, int L, const double *r, double *z)
+// One pass: the output panel filled with the pending pattern (one 32-bit fill), then the solve.
+hipError_t launch_ic0_trsv(const mspmv_ic0_s *ic, bool fwd, const double *d_b, double *d_x, int L, CgControl *ctrl,
+                           hipStream_t s)
 {
     if (ic->n == 0)
         return hipSuccess;
-    for (int pass = 0; pass < 2; ++pass) {
-        const bool fwd = pass == 0;
-        const double *in = fwd ? r : ic->d_y;
-        double *out = fwd ? ic->d_y : z;
-        hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out), kTrsvPendingWord,
-                                         2 * (size_t)ic->n * L, h->stream);
-        if (e != hipSuccess)
-            return e;
-        e = dispatch_L(L, [&](auto Lc) {
-            trsv_L<decltype(Lc)::value>(ic, fwd, in, out, h->d_ctrl, h->stream);
-            return hipGetLastError();
-        });
-        if (e != hipSuccess)
-            return e;
-    }
-    return hipSuccess;
+    hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_x), kTrsvPendingWord, 2 * (size_t)ic->n * L, s);
+    if (e != hipSuccess)
+        return e;
+    return dispatch_L(L, [&](auto Lc) {
+        trsv_L<decltype(Lc)::value>(ic, fwd, d_b, d_x, ctrl, s);
+        return hipGetLastError();
+    });
+}
+
+// Z = L^-T (L^-1 R): ForwardSolveMultiple into ic->d_y, then BackwardSolveMultiple
+// (incomplete_cholesky.hpp:89-92, :166-167), each into a panel pre-filled with the pending pattern.
+static hipError_t ic0_apply(mspmv_handle_s *h, mspmv_ic0_s *ic, int L, const double *r, double *z)
+{
+    hipError_t e = launch_ic0_trsv(ic, true, r, ic->d_y, L, h->d_ctrl, h->stream);
+    if (e == hipSuccess)
+        e = launch_ic0_trsv(ic, false, ic->d_y, z, L, h->d_ctrl, h->stream);
+    return e;
 }
 
 // X = 0, R = B, b_norms (incomplete_cholesky.hpp:66-85); Z = M^-1 R (:87-92); P = Z (:94-95);

@@ -82,6 +82,25 @@ extern "C" MSPMV_API mspmv_status mspmv_ic0_factor(const mspmv_csr_d *a, int *l_
     }
     const int n = a->num_rows;
     const int *ro = a->row_offsets, *ci = a->column_indices;
+    // The merge walk below and "row k's last entry is its diagonal" hold only when each row's
+    // lower part (columns <= row) is strictly ascending and ends in the diagonal: anything else
+    // (unsorted or duplicate columns, a missing diagonal) would factor to garbage with MSPMV_OK.
+    for (int i = 0; i < n; ++i) {
+        int prev = -1;
+        for (int k = ro[i]; k < ro[i + 1]; ++k)
+            if (ci[k] <= i) {
+                if (ci[k] <= prev) {
+                    mspmv::set_error("ic0: row " + std::to_string(i) +
+                                     ": the entries with column <= row must be strictly ascending");
+                    return MSPMV_ERR_INVALID;
+                }
+                prev = ci[k];
+            }
+        if (prev != i) {
+            mspmv::set_error("ic0: row " + std::to_string(i) + " has no diagonal entry");
+            return MSPMV_ERR_INVALID;
+        }
+    }
     l_row_offsets[0] = 0;
     int nz = 0;
     for (int i = 0; i < n; ++i) {  // :91-148

@@ -339,7 +339,7 @@ struct PatternScope {
 }  // namespace mspmv
 
 // IC(0) factor on the device (mspmv_ic0_create): L and its transpose for the two sync-free
-// triangular solves of the preconditioner apply, their ready flags and the intermediate Y.
+// triangular solves of the preconditioner apply, their level orders and the intermediate Y.
 struct mspmv_ic0_s {
     unsigned long long gen = mspmv_next_generation();
     int device = 0;
@@ -351,7 +351,6 @@ struct mspmv_ic0_s {
     int *d_fwd_order = nullptr;              // [n] rows of L by dependency level (then row): wave w solves row fwd_order[w]
     int *d_bwd_order = nullptr;              // [n] rows of L^T by backward level
     int levels_fwd = 0, levels_bwd = 0;
-    int *d_ready = nullptr;                  // [n] per-row ready flags of the running solve
     double *d_y = nullptr;                   // [n * L] forward-solve result
     size_t y_cap = 0;
 };
@@ -639,7 +638,13 @@ hipError_t launch_pcg_init(mspmv_handle_s *h, mspmv_handle_s *hm, const TilePlan
 hipError_t launch_pcg_iteration(mspmv_handle_s *h, mspmv_handle_s *hm, const TilePlan &plan, const TilePlan &mplan,
                                 double *d_x, int L, int nblk, double tol);
 // IC(0)-preconditioned block CG (PCGSolveMultiple, work_2025/main/incomplete_cholesky.hpp:33-199):
-// Z = L^-T L^-1 R by two sync-free triangular solves (k_trsv); ic->d_y must hold m * L.
+// Z = L^-T L^-1 R by two sync-free triangular solves (k_trsv_tagged); ic->d_y must hold m * L.
+// One sync-free triangular solve with the factor, on stream s: d_x (n x L) is filled with the pending
+// pattern, then k_trsv_tagged<L, fwd> solves L X = B (fwd) or L^T X = B.  A dependency that never
+// arrives raises ctrl->breakdown = 2 and ctrl->done.  The pass ic0_apply runs twice per application
+// and mspmv_ic0_solve_dev once.
+hipError_t launch_ic0_trsv(const mspmv_ic0_s *ic, bool fwd, const double *d_b, double *d_x, int L, CgControl *ctrl,
+                           hipStream_t s);
 hipError_t launch_pcg_ic0_init(mspmv_handle_s *h, mspmv_ic0_s *ic, const double *d_b, double *d_x, int L, double tol,
                                int nblk);
 hipError_t launch_pcg_ic0_iteration(mspmv_handle_s *h, mspmv_ic0_s *ic, const TilePlan &plan, double *d_x, int L,

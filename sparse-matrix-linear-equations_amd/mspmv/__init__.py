@@ -110,6 +110,7 @@ _SIGS = {
     "mspmv_ic0_destroy": (_I, [_P]),
     "mspmv_dpcg_ic0_multi": (_I, [_P, _P, _P, _P, _I, _I, _D, _I, _PI, _P, _I]),
     "mspmv_dpcg_ic0_multi_dev": (_I, [_P, _P, _P, _P, _I, _I, _D, _I, _PI, _P, _I]),
+    "mspmv_ic0_solve_dev": (_I, [_P, _P, _I, _P, _P, _I]),
     "mspmv_dpcg_spai_multi": (_I, [_P, _P, _P, _P, _I, _I, _D, _I, _PI, _P, _I]),
     "mspmv_dpcg_spai_multi_dev": (_I, [_P, _P, _P, _P, _I, _I, _D, _I, _PI, _P, _I]),
     "mspmv_time_spmm_dev": (_I, [_P, _P, _P, _I, _I, _SZ, _PD]),
@@ -677,6 +678,15 @@ def ic0_factor(a: CsrMatrix):
     return CsrMatrix.from_arrays(a.num_cols, ro, ci[: nz.value], va[: nz.value]), sh.value
 
 
+def csr_transpose(a: CsrMatrix) -> CsrMatrix:
+    """TransposeCsr (mspmv_csr_transpose) on the host: A^T in CSR, columns ascending in each row."""
+    ro = np.zeros(a.num_cols + 1, np.int32)
+    ci = np.zeros(max(a.num_nonzeros, 1), np.int32)
+    va = np.zeros(max(a.num_nonzeros, 1), np.float64)
+    _check(lib.mspmv_csr_transpose(ctypes.byref(a._c()), _ptr(ro), _ptr(ci), _ptr(va)), "csr_transpose")
+    return CsrMatrix.from_arrays(a.num_rows, ro, ci[: a.num_nonzeros], va[: a.num_nonzeros])
+
+
 class GpuIc0:
     """An IC(0) factor L (and L^T) resident on a device for the GPU triangular solves."""
 
@@ -684,7 +694,28 @@ class GpuIc0:
         h = ctypes.c_void_p()
         _check(lib.mspmv_ic0_create(ctypes.byref(l._c()), device, ctypes.byref(h)), "ic0_create")
         self.h = h.value
+        self.device = device
         _track(self)
+
+    def solve_dev(self, g: "GpuCsr", dB: "DeviceBuffer", dX: "DeviceBuffer", L: int, transpose: bool = False) -> int:
+        """mspmv_ic0_solve_dev on device panels: one triangular solve, L X = B or L^T X = B."""
+        return _check(lib.mspmv_ic0_solve_dev(g.h, self.h, int(bool(transpose)), dB.ptr, dX.ptr, L), "ic0_solve_dev")
+
+    def solve(self, g: "GpuCsr", B: np.ndarray, transpose: bool = False) -> np.ndarray:
+        """One triangular solve with the factor on g's stream (mspmv_ic0_solve_dev): X with L X = B, or
+        L^T X = B (transpose), for a host panel B [n] or [n, L], L in SUPPORTED_L."""
+        B = np.ascontiguousarray(B, np.float64)
+        shape = B.shape
+        if B.ndim == 1:
+            B = B[:, None]
+        dB = DeviceBuffer.from_array(B, self.device) if B.size else DeviceBuffer(16, self.device)
+        dX = DeviceBuffer(max(B.nbytes, 16), self.device)
+        try:
+            self.solve_dev(g, dB, dX, B.shape[1], transpose)
+            return dX.download(B.shape).reshape(shape)
+        finally:
+            dB.free()
+            dX.free()
 
     def close(self):
         if getattr(self, "h", None):
