@@ -43,7 +43,7 @@ typedef enum mspmv_status {
     MSPMV_ERR_RCCL = 5,          /* a collective failed */
     MSPMV_ERR_UNSUPPORTED = 6,   /* e.g. L outside the compiled set */
     MSPMV_ERR_IO = 7,            /* MatrixMarket read/parse failure */
-    MSPMV_ERR_STALL = 8,         /* IC(0) apply: a triangular-solve dependency never became ready
+    MSPMV_ERR_STALL = 8,         /* IC(0) / ILU(0) apply: a triangular-solve dependency never became ready
                                     (the solve stopped; X is not a solution) */
     MSPMV_ERR_FAULT = 9          /* a cross-workgroup fold ticket drew past its group: its array was
                                     not zero when the launch began, so a fold summed partials not yet
@@ -65,6 +65,9 @@ typedef struct mspmv_csr_d {
 typedef struct mspmv_handle_s *mspmv_handle;
 /* An IC(0) factor resident on a device (mspmv_ic0_create). */
 typedef struct mspmv_ic0_s *mspmv_ic0;
+/* An ILU(0) factor resident on a device (mspmv_ilu0_create).  A type of its own: a nonsymmetric
+ * factor cannot be handed to the PCG. */
+typedef struct mspmv_ilu0_s *mspmv_ilu0;
 
 /* Merge-path coordinate (CUB CoordinateT / the reference's int2, types.hpp:3-7). */
 typedef struct mspmv_coord {
@@ -182,7 +185,8 @@ MSPMV_API mspmv_status mspmv_dcg_multi_dev(mspmv_handle h, const double *d_B, do
 
 /* ---- BiCGSTAB (nonsymmetric systems) -------------------------------------------------- */
 /* Multi-RHS BiCGSTAB for a square matrix that need not be symmetric or definite (van der
- * Vorst's recurrence, unpreconditioned, shadow residual rhat = b); only A X is needed, no
+ * Vorst's recurrence, unpreconditioned -- mspmv_dpbicgstab_ilu0_multi below is the preconditioned
+ * form -- shadow residual rhat = b); only A X is needed, no
  * transpose.  No reference counterpart (every solver of the reference is a CG).  Per column j of
  * the interleaved n x L panels: X = 0, R = P = B, rho = B.B; per iteration V = A P,
  * alpha = rho / (rhat.V), s = R - alpha V, X += alpha P, T = A s, omega = T.s / T.T (T.T == 0:
@@ -268,6 +272,51 @@ MSPMV_API mspmv_status mspmv_dpcg_ic0_multi_dev(mspmv_handle a, mspmv_ic0 m, con
  * MSPMV_ERR_UNSUPPORTED for another L. */
 MSPMV_API mspmv_status mspmv_ic0_solve_dev(mspmv_handle a, mspmv_ic0 m, int transpose, const double *d_B,
                                            double *d_X, int L);
+
+/* ---- ILU(0)-preconditioned BiCGSTAB (nonsymmetric systems) ---------------------------- */
+/* ILU(0) on the host, in A's own pattern, row by row in IKJ order: for each entry (i, k) of row i
+ * with k < i, ascending, l = w(k) / U(k,k), w(k) = l, w(j) -= l U(k,j) for every j > k held by
+ * both rows' patterns (every l * u and the subtraction round separately).  lu_values[num_nonzeros]
+ * receives the factors in A's CSR order, like mspmv_spai_values: entries with column < row hold L's
+ * multipliers (unit diagonal implied), entries with column >= row hold U.  Sequential, like
+ * mspmv_ic0_factor.  No reference counterpart (the reference has no ILU), so no diagonal shifting:
+ * a zero or non-finite pivot is MSPMV_ERR_BREAKDOWN, the message naming the row.
+ * Precondition, checked first: A is square and every row's columns ascend strictly (sorted, no
+ * duplicates) and hold the diagonal.  Anything else is MSPMV_ERR_INVALID, the message naming the
+ * first such row. */
+MSPMV_API mspmv_status mspmv_ilu0_values(const mspmv_csr_d *a, double *lu_values);
+/* Upload the factor for the GPU triangular solves: `lu` is A's pattern with mspmv_ilu0_values'
+ * values, split into L (the strictly lower entries and a stored 1.0 diagonal, last in its row) and
+ * U (the diagonal first, then the upper entries), each with its dependency-level order.  The row
+ * checks of mspmv_ilu0_values apply; a zero or non-finite diagonal is MSPMV_ERR_INVALID (a solve
+ * must never divide by it).  All of that is checked before the device is touched. */
+MSPMV_API mspmv_status mspmv_ilu0_create(const mspmv_csr_d *lu, int device, mspmv_ilu0 *out);
+MSPMV_API mspmv_status mspmv_ilu0_destroy(mspmv_ilu0 m);
+/* One triangular solve with the factor: upper = 0 solves L X = B (unit diagonal), 1 solves
+ * U X = B.  The contract of mspmv_ic0_solve_dev, check for check: device panels n x L row-major,
+ * 16-byte aligned, not overlapping, L in {1,2,4,8,16} (MSPMV_ERR_UNSUPPORTED otherwise); a factor of
+ * another shape or device is MSPMV_ERR_INVALID; MSPMV_ERR_STALL as the solver reports it; X is
+ * untouched on a rejected call. */
+MSPMV_API mspmv_status mspmv_ilu0_solve_dev(mspmv_handle a, mspmv_ilu0 m, int upper, const double *d_B,
+                                            double *d_X, int L);
+/* Right-preconditioned multi-RHS BiCGSTAB with M = L U.  The residual is the original system's, so
+ * the stop test and the history mean what they mean in mspmv_dbicgstab_multi.  Per column, X = 0,
+ * R = Rhat = P = B, rho = B.B; per iteration Phat = U^-1 L^-1 P, V = A Phat, alpha = rho / (Rhat.V),
+ * s = R - alpha V, X += alpha Phat, Shat = U^-1 L^-1 s, T = A Shat, omega = T.s / T.T (T.T == 0:
+ * omega = 0, not a breakdown), X += omega Shat, R = s - omega T, stop test on sqrt(R.R)/||B_j||,
+ * rho' = Rhat.R, beta = (rho'/rho)(alpha/omega), P = R + beta (P - omega V).  Masks, the per-column
+ * freeze (MSPMV_ERR_BREAKDOWN with the other columns solved), ||B_j|| == 0 -> 1, the history, the
+ * iteration count and any L >= 1 are mspmv_dbicgstab_multi's.  An iteration is two products, four
+ * sync-free triangular solves (as mspmv_dpcg_ic0_multi's) and five streaming passes; a stalled
+ * triangular solve stops the iteration and is reported as MSPMV_ERR_STALL, never a hang.
+ * MSPMV_ERR_INVALID for a null factor, a factor of another shape or device, a non-square matrix,
+ * max_iters < 0, null vectors, or device vectors not 16-byte aligned.  No reference counterpart. */
+MSPMV_API mspmv_status mspmv_dpbicgstab_ilu0_multi(mspmv_handle a, mspmv_ilu0 m, const double *B, double *X, int L,
+                                                   int max_iters, double tolerance, int *iters,
+                                                   double *max_err_hist, int hist_cap);
+MSPMV_API mspmv_status mspmv_dpbicgstab_ilu0_multi_dev(mspmv_handle a, mspmv_ilu0 m, const double *d_B, double *d_X,
+                                                       int L, int max_iters, double tolerance, int *iters,
+                                                       double *max_err_hist, int hist_cap);
 
 /* ---- measurement helpers (HIP events on the handle's stream) ------------------------ */
 /* Enqueue `reps` back-to-back SpMV (L == 1) or SpMM launches on device buffers and return

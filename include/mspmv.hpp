@@ -132,6 +132,12 @@ inline std::map<Key, mspmv_ic0> &factors()
     return c;
 }
 
+inline std::map<Key, mspmv_ilu0> &ilu_factors()  // by the key of the matrix factored
+{
+    static std::map<Key, mspmv_ilu0> c;
+    return c;
+}
+
 template <typename Csr>
 mspmv_csr_d view(const Csr &a)
 {
@@ -186,6 +192,25 @@ mspmv_ic0 ic0_for(const Csr &l)
     return f;
 }
 
+// The ILU(0) factor of `a` itself (mspmv_ilu0_values on the host, then mspmv_ilu0_create), cached with it.
+template <typename Csr>
+mspmv_ilu0 ilu0_for(const Csr &a)
+{
+    const Key k = key_of(a);
+    auto it = ilu_factors().find(k);
+    if (it != ilu_factors().end())
+        return it->second;
+    evict_same_arrays<mspmv_ilu0>(ilu_factors(), k, [](mspmv_ilu0 f) { (void)mspmv_ilu0_destroy(f); });
+    mspmv_csr_d d = view(a);
+    std::vector<double> lu((size_t)std::max<long long>(a.num_nonzeros, 1));
+    check(mspmv_ilu0_values(&d, lu.data()), "mspmv_ilu0_values");
+    d.values = lu.data();
+    mspmv_ilu0 f = nullptr;
+    check(mspmv_ilu0_create(&d, device(), &f), "mspmv_ilu0_create");
+    ilu_factors().emplace(k, f);
+    return f;
+}
+
 // Device buffer (RAII) for the harnesses: inputs resident in HBM across timed repetitions.
 struct DevBuf {
     void *p = nullptr;
@@ -237,14 +262,15 @@ double wall_ms(F &&f)
 
 }  // namespace detail
 
-// Forget the device copy (handle or IC(0) factor) of a matrix: call after mutating it in place
-// or before freeing it if its buffers will be reused.
+// Forget the device copy (handle, IC(0) factor, or the ILU(0) factor computed from it) of a matrix: call
+// after mutating it in place or before freeing it if its buffers will be reused.
 template <typename Csr>
 void release(const Csr &a)
 {
     const detail::Key k = detail::key_of(a);
     detail::evict_same_arrays<mspmv_handle>(detail::handles(), k, [](mspmv_handle h) { (void)mspmv_destroy(h); });
     detail::evict_same_arrays<mspmv_ic0>(detail::factors(), k, [](mspmv_ic0 f) { (void)mspmv_ic0_destroy(f); });
+    detail::evict_same_arrays<mspmv_ilu0>(detail::ilu_factors(), k, [](mspmv_ilu0 f) { (void)mspmv_ilu0_destroy(f); });
 }
 inline void release_all()
 {
@@ -252,8 +278,11 @@ inline void release_all()
         (void)mspmv_destroy(e.second);
     for (auto &e : detail::factors())
         (void)mspmv_ic0_destroy(e.second);
+    for (auto &e : detail::ilu_factors())
+        (void)mspmv_ilu0_destroy(e.second);
     detail::handles().clear();
     detail::factors().clear();
+    detail::ilu_factors().clear();
 }
 
 // ---- kernels ---------------------------------------------------------------------------------
@@ -311,6 +340,23 @@ int BiCGStabSolveMultiple(Csr &a, const ValueT *B, ValueT *X, int num_vectors, i
     detail::note_cg(mspmv_dbicgstab_multi(detail::handle_for(a), B, X, num_vectors, max_iters, tolerance, &iters,
                                           max_errors ? hist.data() : nullptr, max_errors ? max_iters : 0),
                     "BiCGStabSolveMultiple");
+    if (max_errors)
+        max_errors->assign(hist.begin(), hist.begin() + std::min<size_t>(hist.size(), (size_t)iters));
+    return iters;
+}
+
+// The same right-preconditioned with the ILU(0) factor of `a` (mspmv_dpbicgstab_ilu0_multi); the factor is
+// computed on the first call and cached with the matrix's handle.  No reference counterpart.
+template <typename Csr, typename ValueT>
+int ILU0BiCGStabSolveMultiple(Csr &a, const ValueT *B, ValueT *X, int num_vectors, int max_iters, ValueT tolerance,
+                              std::vector<double> *max_errors = nullptr)
+{
+    int iters = 0;
+    std::vector<double> hist(max_errors ? (size_t)std::max(max_iters, 0) : 0);
+    detail::note_cg(mspmv_dpbicgstab_ilu0_multi(detail::handle_for(a), detail::ilu0_for(a), B, X, num_vectors,
+                                                max_iters, tolerance, &iters, max_errors ? hist.data() : nullptr,
+                                                max_errors ? max_iters : 0),
+                    "ILU0BiCGStabSolveMultiple");
     if (max_errors)
         max_errors->assign(hist.begin(), hist.begin() + std::min<size_t>(hist.size(), (size_t)iters));
     return iters;
@@ -640,6 +686,12 @@ int BiCGStabSolveMultiple(CsrMatrix<ValueT, OffsetT> &a, const ValueT *B, ValueT
                           ValueT tolerance, std::vector<double> *max_errors = nullptr)
 {
     return mspmv_ref::BiCGStabSolveMultiple(a, B, X, num_vectors, max_iters, tolerance, max_errors);
+}
+template <typename ValueT, typename OffsetT>
+int ILU0BiCGStabSolveMultiple(CsrMatrix<ValueT, OffsetT> &a, const ValueT *B, ValueT *X, int num_vectors,
+                              int max_iters, ValueT tolerance, std::vector<double> *max_errors = nullptr)
+{
+    return mspmv_ref::ILU0BiCGStabSolveMultiple(a, B, X, num_vectors, max_iters, tolerance, max_errors);
 }
 template <typename ValueT, typename OffsetT>
 void TestCGMultipleRHS(CsrMatrix<ValueT, OffsetT> &a, ValueT *b_vectors, ValueT *x_solutions, int max_iters,

@@ -1134,6 +1134,10 @@ mspmv_status mspmv_destroy(mspmv_handle h)
         (void)hipGraphExecDestroy(h->bicg_exec);
     if (h->bicg_graph)
         (void)hipGraphDestroy(h->bicg_graph);
+    if (h->pbicg_exec)
+        (void)hipGraphExecDestroy(h->pbicg_exec);
+    if (h->pbicg_graph)
+        (void)hipGraphDestroy(h->pbicg_graph);
     if (h->d_flush)
         (void)hipFree(h->d_flush);
     if (h->h_ctrl)
@@ -1223,12 +1227,19 @@ mspmv_status mspmv_set_cu_limit(mspmv_handle h, int num_cus)
         (void)hipGraphExecDestroy(h->bicg_exec);
     if (h->bicg_graph)
         (void)hipGraphDestroy(h->bicg_graph);
+    if (h->pbicg_exec)
+        (void)hipGraphExecDestroy(h->pbicg_exec);
+    if (h->pbicg_graph)
+        (void)hipGraphDestroy(h->pbicg_graph);
     h->cg_exec = nullptr;
     h->cg_graph = nullptr;
     h->cg_graph_key.clear();
     h->bicg_exec = nullptr;
     h->bicg_graph = nullptr;
     h->bicg_graph_key.clear();
+    h->pbicg_exec = nullptr;
+    h->pbicg_graph = nullptr;
+    h->pbicg_graph_key.clear();
     if (h->own_stream)
         (void)hipStreamDestroy(h->stream);
     h->stream = s;
@@ -1993,15 +2004,43 @@ static mspmv_status cg_solve_dev(mspmv_handle_s *h, const double *d_b, double *d
         "CG breakdown: p.Ap gave a non-finite alpha in at least one column (frozen; the other columns were solved)");
 }
 
+// The ILU(0) factor's two n x L panels (the apply's intermediate tri.d_y and the hat panel), grown on demand.
+static mspmv_status ilu0_workspace(mspmv_ilu0_s *ilu, size_t elems)
+{
+    HIP_TRY(hipSetDevice(ilu->tri.device));
+    if (elems > ilu->tri.y_cap) {
+        if (ilu->tri.d_y)
+            (void)hipFree(ilu->tri.d_y);
+        ilu->tri.d_y = nullptr;
+        ilu->tri.y_cap = 0;
+        if (hipMalloc(&ilu->tri.d_y, sizeof(double) * elems) != hipSuccess)
+            return (set_error("ILU(0) workspace allocation failed"), MSPMV_ERR_OOM);
+        ilu->tri.y_cap = elems;
+    }
+    if (elems > ilu->hat_cap) {
+        dev_free(ilu->d_hat);
+        ilu->d_hat = nullptr;
+        ilu->hat_cap = 0;
+        ST_TRY(dev_alloc(&ilu->d_hat, elems));
+        ilu->hat_cap = elems;
+    }
+    return MSPMV_OK;
+}
+
 // BiCGSTAB on a panel of native width (mspmv_bicgstab.hip), by cg_solve_native's protocol: control word and
 // tickets zeroed on the handle's stream before the init, iterations in batches of cg_batch_iters with the
 // control word copied back per batch, a batch replayed as a graph captured from the handle's one stream (a
 // linear chain) and cached under the solver's own exec and key; fewer than a batch of iterations run ungraphed.
+// ilu: the ILU(0) factor of the right-preconditioned form (launch_pbicgstab_iteration), else null.  The two forms
+// share the handle's workspace and keep a cached graph each, so neither replays nor evicts the other's.
 static mspmv_status bicgstab_solve_native(mspmv_handle_s *h, const double *d_b, double *d_x, int L, int max_iters,
-                                          double tol, int *iters, double *hist, int hist_cap)
+                                          double tol, int *iters, double *hist, int hist_cap,
+                                          mspmv_ilu0_s *ilu = nullptr)
 {
     if (h->m != h->n)
         return invalid("BiCGSTAB needs a square matrix");
+    if (ilu && (ilu->tri.n != h->m || ilu->tri.device != h->device))
+        return invalid("the ILU(0) factor must match the matrix's shape and device");
     if (!supported_L(L))
         return (set_error("L must be one of 1, 2, 4, 8, 16"), MSPMV_ERR_UNSUPPORTED);
     if (max_iters < 0)
@@ -2032,7 +2071,10 @@ static mspmv_status bicgstab_solve_native(mspmv_handle_s *h, const double *d_b, 
         ST_TRY(dev_alloc(&h->d_rhat, elems));
         h->rhat_cap = elems;
     }
-    h->last_cg_kernel = "BiCGSTAB (2 SpMM + 5 passes)";
+    if (ilu)  // the apply's intermediate and the hat panel live with the factor: grown here, before any capture
+        ST_TRY(ilu0_workspace(ilu, elems));
+    const char *name = ilu ? "ILU0-BiCGSTAB" : "BiCGSTAB";
+    h->last_cg_kernel = ilu ? "ILU0-BiCGSTAB (2 SpMM + 4 trsv + 5 passes)" : "BiCGSTAB (2 SpMM + 5 passes)";
     const int use_cap = hist ? cap : 0;
     const int saved_cap = h->hist_cap;
     h->hist_cap = use_cap;  // kernels record only what the caller asked for
@@ -2040,26 +2082,43 @@ static mspmv_status bicgstab_solve_native(mspmv_handle_s *h, const double *d_b, 
     ST_TRY(solve_prologue(h, {plan, splan}, &poison));
     HIP_TRY(launch_bicgstab_init(h, d_b, d_x, L, tol, nblk));
     ST_TRY(solve_poison_fill(h, poison));
-    auto iterate = [&](int) -> hipError_t { return launch_bicgstab_iteration(h, *plan, splan, d_x, L, nblk, tol); };
+    auto iterate = [&](int) -> hipError_t {
+        if (ilu)
+            return launch_pbicgstab_iteration(h, ilu, *plan, splan, d_x, L, nblk, tol);
+        return launch_bicgstab_iteration(h, *plan, splan, d_x, L, nblk, tol);
+    };
     const int K = cg_batch_iters(h->m, h->nnz, L);
     mspmv_status st = MSPMV_OK;
     hipGraphExec_t exec = nullptr;
     if (max_iters >= K && !(poison & MSPMV_POISON_LATE_ZERO)) {
         const void *tk = nullptr;
         std::memcpy(&tk, &tol, sizeof tk);
-        const std::vector<const void *> key = {
+        std::vector<const void *> key = {
             d_x, h->d_r, h->d_rhat, h->d_p0, h->d_p1, h->d_ap, h->d_partials, h->d_gtickets, h->d_scal, h->d_conv,
             h->d_red, h->d_ctrl, h->d_hist, h->stream, plan, splan, tk,
             reinterpret_cast<const void *>((intptr_t)L), reinterpret_cast<const void *>((intptr_t)nblk),
             reinterpret_cast<const void *>((intptr_t)use_cap), reinterpret_cast<const void *>((intptr_t)K)};
-        st = solver_graph(h, SolverGraph{h->bicg_graph, h->bicg_exec, h->bicg_graph_key}, key, K, iterate, "BiCGSTAB");
-        exec = h->bicg_exec;
+        if (ilu) {  // the factor, its generation, its value arrays, its workspace
+            key.insert(key.end(), {ilu, reinterpret_cast<const void *>((uintptr_t)ilu->tri.gen), ilu->tri.d_lva,
+                                   ilu->tri.d_uva, ilu->tri.d_y, ilu->d_hat});
+            st = solver_graph(h, SolverGraph{h->pbicg_graph, h->pbicg_exec, h->pbicg_graph_key}, key, K, iterate, name);
+            exec = h->pbicg_exec;
+        } else {
+            st = solver_graph(h, SolverGraph{h->bicg_graph, h->bicg_exec, h->bicg_graph_key}, key, K, iterate, name);
+            exec = h->bicg_exec;
+        }
     }
     hipEvent_t evs[2] = {nullptr, nullptr};
     if (st == MSPMV_OK)
-        st = solve_batches(h, K, max_iters, exec, poison, evs, "BiCGSTAB", iterate);
+        st = solve_batches(h, K, max_iters, exec, poison, evs, name, iterate);
     CgControl fin{};
-    ST_TRY(solve_collect(h, st, evs, saved_cap, use_cap, iters, hist, &fin, "BiCGSTAB"));
+    ST_TRY(solve_collect(h, st, evs, saved_cap, use_cap, iters, hist, &fin, name));
+    if (fin.breakdown == 2) {  // set by a triangular solve; a column freeze never overwrites it
+        if (iters)
+            *iters = fin.iter;
+        set_error("ILU(0) apply: a triangular-solve dependency never became ready (solve stalled)");
+        return MSPMV_ERR_STALL;
+    }
     if (fin.breakdown) {
         set_error("BiCGSTAB breakdown: a non-finite alpha, omega or beta in at least one column (frozen; the other "
                   "columns were solved)");
@@ -2069,14 +2128,15 @@ static mspmv_status bicgstab_solve_native(mspmv_handle_s *h, const double *d_b, 
 }
 
 static mspmv_status bicgstab_solve_dev(mspmv_handle_s *h, const double *d_b, double *d_x, int L, int max_iters,
-                                       double tol, int *iters, double *hist, int hist_cap)
+                                       double tol, int *iters, double *hist, int hist_cap,
+                                       mspmv_ilu0_s *ilu = nullptr)
 {
     return solve_dev_groups(
         h, d_b, d_x, L, iters, hist, hist_cap,
         [&](const double *b, double *x, int w, int *it, double *hg, int cap) {
-            return bicgstab_solve_native(h, b, x, w, max_iters, tol, it, hg, cap);
+            return bicgstab_solve_native(h, b, x, w, max_iters, tol, it, hg, cap, ilu);
         },
-        "BiCGSTAB",
+        ilu ? "ILU0-BiCGSTAB" : "BiCGSTAB",
         "BiCGSTAB breakdown: a non-finite alpha, omega or beta in at least one column (frozen; the other columns "
         "were solved)");
 }
@@ -2205,6 +2265,27 @@ mspmv_status mspmv_dbicgstab_multi(mspmv_handle h, const double *B, double *X, i
     });
 }
 
+mspmv_status mspmv_dpbicgstab_ilu0_multi_dev(mspmv_handle a, mspmv_ilu0 m, const double *d_B, double *d_X, int L,
+                                             int max_iters, double tolerance, int *iters, double *max_err_hist,
+                                             int hist_cap)
+{
+    ST_TRY(check_handle(a));
+    if (!m)
+        return invalid("null ILU(0) factor");
+    return bicgstab_solve_dev(a, d_B, d_X, L, max_iters, tolerance, iters, max_err_hist, hist_cap, m);
+}
+
+mspmv_status mspmv_dpbicgstab_ilu0_multi(mspmv_handle a, mspmv_ilu0 m, const double *B, double *X, int L,
+                                         int max_iters, double tolerance, int *iters, double *max_err_hist,
+                                         int hist_cap)
+{
+    if (!m)
+        return invalid("null ILU(0) factor");
+    return solve_host(a, B, X, L, iters, [&](const double *dB, double *dX) {
+        return bicgstab_solve_dev(a, dB, dX, L, max_iters, tolerance, iters, max_err_hist, hist_cap, m);
+    });
+}
+
 mspmv_status mspmv_dpcg_spai_multi_dev(mspmv_handle a, mspmv_handle m, const double *d_B, double *d_X, int L,
                                        int max_iters, double tolerance, mspmv_spmm_kernel kernel, int *iters,
                                        double *max_err_hist, int hist_cap)
@@ -2225,6 +2306,74 @@ mspmv_status mspmv_dpcg_spai_multi(mspmv_handle a, mspmv_handle m, const double 
 }
 
 // ---- IC(0) factor on the device --------------------------------------------------------------
+// Two triangular CSRs on the device for the sync-free solves (launch_ic0_trsv): a lower one solved forward
+// (diagonal present in every row) and an upper one solved backward, with their level orders.  IC(0) passes L
+// and its transpose, ILU(0) passes L (unit diagonal stored) and U.
+// Level sets: a row's level is 1 + the deepest level among the rows it reads (L: columns
+// below the diagonal, solved ascending; L^T: columns above it, solved descending).  Waves
+// take rows in (level, row) order, so every awaited row is in an earlier level, hence an
+// earlier-dispatched wave, and a whole level's rows are solved concurrently (natural order
+// would chain every row to its left neighbour: ~15x slower on a 2-D stencil).
+static mspmv_status upload_triangles(int n, const int *lro, const int *lci, const double *lva, int lnnz,
+                                     const int *uro, const int *uci, const double *uva, int unnz, int device,
+                                     mspmv_ic0_s *m, const char *what)
+{
+    auto order_by_level = [&](const int *rp, const int *cp, bool fwd, std::vector<int> &order) {
+        std::vector<int> lev((size_t)n, 0);
+        int maxlev = 0;
+        for (int s = 0; s < n; ++s) {
+            const int i = fwd ? s : n - 1 - s;
+            int lv = 0;
+            for (int k = rp[i]; k < rp[i + 1]; ++k) {
+                const int j = cp[k];
+                if (fwd ? j < i : j > i)
+                    lv = std::max(lv, lev[j] + 1);
+            }
+            lev[i] = lv;
+            maxlev = std::max(maxlev, lv);
+        }
+        std::vector<int> cnt((size_t)maxlev + 2, 0);
+        for (int i = 0; i < n; ++i)
+            ++cnt[(size_t)lev[i] + 1];
+        for (int l2 = 0; l2 <= maxlev; ++l2)
+            cnt[(size_t)l2 + 1] += cnt[l2];
+        order.assign((size_t)std::max(n, 1), 0);
+        for (int s = 0; s < n; ++s) {
+            const int i = fwd ? s : n - 1 - s;
+            order[(size_t)cnt[lev[i]]++] = i;
+        }
+        return n ? maxlev + 1 : 0;
+    };
+    std::vector<int> fwd_order, bwd_order;
+    const int lf = order_by_level(lro, lci, true, fwd_order);
+    const int lb = order_by_level(uro, uci, false, bwd_order);
+    HIP_TRY(hipSetDevice(device));
+    m->levels_fwd = lf;
+    m->levels_bwd = lb;
+    m->device = device;
+    m->n = n;
+    m->nnz = lnnz;
+    mspmv_status st = MSPMV_OK;
+    auto up = [&](auto **d, const auto *src, size_t cnt) {
+        if (st != MSPMV_OK)
+            return;
+        st = dev_alloc(d, std::max<size_t>(cnt, 1));
+        if (st == MSPMV_OK && cnt && hipMemcpy(*d, src, sizeof(**d) * cnt, hipMemcpyHostToDevice) != hipSuccess) {
+            set_error(std::string(what) + " upload failed");
+            st = MSPMV_ERR_HIP;
+        }
+    };
+    up(&m->d_lro, lro, (size_t)n + 1);
+    up(&m->d_lci, lci, (size_t)lnnz);
+    up(&m->d_lva, lva, (size_t)lnnz);
+    up(&m->d_uro, uro, (size_t)n + 1);
+    up(&m->d_uci, uci, (size_t)unnz);
+    up(&m->d_uva, uva, (size_t)unnz);
+    up(&m->d_fwd_order, fwd_order.data(), (size_t)n);
+    up(&m->d_bwd_order, bwd_order.data(), (size_t)n);
+    return st;
+}
+
 mspmv_status mspmv_ic0_create(const mspmv_csr_d *l, int device, mspmv_ic0 *out)
 {
     if (!out)
@@ -2272,65 +2421,9 @@ mspmv_status mspmv_ic0_create(const mspmv_csr_d *l, int device, mspmv_ic0 *out)
                 uva[d] = l->values[k];
             }
     }
-    // Level sets: a row's level is 1 + the deepest level among the rows it reads (L: columns
-    // below the diagonal, solved ascending; L^T: columns above it, solved descending).  Waves
-    // take rows in (level, row) order, so every awaited row is in an earlier level, hence an
-    // earlier-dispatched wave, and a whole level's rows are solved concurrently (natural order
-    // would chain every row to its left neighbour: ~15x slower on a 2-D stencil).
-    auto order_by_level = [&](const int *rp, const int *cp, bool fwd, std::vector<int> &order) {
-        std::vector<int> lev((size_t)n, 0);
-        int maxlev = 0;
-        for (int s = 0; s < n; ++s) {
-            const int i = fwd ? s : n - 1 - s;
-            int lv = 0;
-            for (int k = rp[i]; k < rp[i + 1]; ++k) {
-                const int j = cp[k];
-                if (fwd ? j < i : j > i)
-                    lv = std::max(lv, lev[j] + 1);
-            }
-            lev[i] = lv;
-            maxlev = std::max(maxlev, lv);
-        }
-        std::vector<int> cnt((size_t)maxlev + 2, 0);
-        for (int i = 0; i < n; ++i)
-            ++cnt[(size_t)lev[i] + 1];
-        for (int l2 = 0; l2 <= maxlev; ++l2)
-            cnt[(size_t)l2 + 1] += cnt[l2];
-        order.assign((size_t)std::max(n, 1), 0);
-        for (int s = 0; s < n; ++s) {
-            const int i = fwd ? s : n - 1 - s;
-            order[(size_t)cnt[lev[i]]++] = i;
-        }
-        return n ? maxlev + 1 : 0;
-    };
-    std::vector<int> fwd_order, bwd_order;
-    const int lf = order_by_level(l->row_offsets, l->column_indices, true, fwd_order);
-    const int lb = order_by_level(uro.data(), uci.data(), false, bwd_order);
-    HIP_TRY(hipSetDevice(device));
     mspmv_ic0_s *m = new mspmv_ic0_s;
-    m->levels_fwd = lf;
-    m->levels_bwd = lb;
-    m->device = device;
-    m->n = n;
-    m->nnz = nnz;
-    mspmv_status st = MSPMV_OK;
-    auto up = [&](auto **d, const auto *src, size_t cnt) {
-        if (st != MSPMV_OK)
-            return;
-        st = dev_alloc(d, std::max<size_t>(cnt, 1));
-        if (st == MSPMV_OK && cnt && hipMemcpy(*d, src, sizeof(**d) * cnt, hipMemcpyHostToDevice) != hipSuccess) {
-            set_error("IC(0) upload failed");
-            st = MSPMV_ERR_HIP;
-        }
-    };
-    up(&m->d_lro, l->row_offsets, (size_t)n + 1);
-    up(&m->d_lci, l->column_indices, (size_t)nnz);
-    up(&m->d_lva, l->values, (size_t)nnz);
-    up(&m->d_uro, uro.data(), (size_t)n + 1);
-    up(&m->d_uci, uci.data(), (size_t)nnz);
-    up(&m->d_uva, uva.data(), (size_t)nnz);
-    up(&m->d_fwd_order, fwd_order.data(), (size_t)n);
-    up(&m->d_bwd_order, bwd_order.data(), (size_t)n);
+    const mspmv_status st = upload_triangles(n, l->row_offsets, l->column_indices, l->values, nnz, uro.data(),
+                                             uci.data(), uva.data(), nnz, device, m, "IC(0)");
     if (st != MSPMV_OK) {
         mspmv_ic0_destroy(m);
         return st;
@@ -2339,10 +2432,9 @@ mspmv_status mspmv_ic0_create(const mspmv_csr_d *l, int device, mspmv_ic0 *out)
     return MSPMV_OK;
 }
 
-mspmv_status mspmv_ic0_destroy(mspmv_ic0 m)
+// The device arrays of a factor's two triangles and its intermediate.
+static void ic0_release(mspmv_ic0_s *m)
 {
-    if (!m)
-        return MSPMV_OK;
     (void)hipSetDevice(m->device);
     dev_free(m->d_lro);
     dev_free(m->d_lci);
@@ -2354,6 +2446,13 @@ mspmv_status mspmv_ic0_destroy(mspmv_ic0 m)
     dev_free(m->d_bwd_order);
     if (m->d_y)
         (void)hipFree(m->d_y);
+}
+
+mspmv_status mspmv_ic0_destroy(mspmv_ic0 m)
+{
+    if (!m)
+        return MSPMV_OK;
+    ic0_release(m);
     delete m;
     return MSPMV_OK;
 }
@@ -2379,17 +2478,18 @@ mspmv_status mspmv_dpcg_ic0_multi(mspmv_handle a, mspmv_ic0 m, const double *B, 
     return cg_solve_host(a, B, X, L, max_iters, tolerance, iters, max_err_hist, hist_cap, nullptr, m);
 }
 
-// One triangular solve with the factor, alone: the pass the PCG's preconditioner apply runs twice
-// (launch_ic0_trsv), on a's stream with a's control word, synchronised.
-mspmv_status mspmv_ic0_solve_dev(mspmv_handle a, mspmv_ic0 m, int transpose, const double *d_B, double *d_X, int L)
+// One triangular solve with a factor, alone: the pass the preconditioner applies run (launch_ic0_trsv), on a's
+// stream with a's control word, synchronised.  what: "IC(0)" / "ILU(0)"; which_msg: the selector's error text.
+static mspmv_status tri_solve_dev(mspmv_handle a, const mspmv_ic0_s *m, int which, const double *d_B, double *d_X,
+                                  int L, const char *what, const char *which_msg)
 {
     ST_TRY(check_handle(a));
     if (!m)
-        return invalid("null IC(0) factor");
-    if (transpose != 0 && transpose != 1)
-        return invalid("transpose must be 0 (L X = B) or 1 (L^T X = B)");
+        return invalid(std::string("null ") + what + " factor");
+    if (which != 0 && which != 1)
+        return invalid(which_msg);
     if (a->m != a->n || m->n != a->m || m->device != a->device)
-        return invalid("the IC(0) factor must match the matrix's shape and device");
+        return invalid(std::string("the ") + what + " factor must match the matrix's shape and device");
     if (!supported_L(L))
         return (set_error("L must be one of 1, 2, 4, 8, 16"), MSPMV_ERR_UNSUPPORTED);
     if (m->n == 0)
@@ -2404,15 +2504,78 @@ mspmv_status mspmv_ic0_solve_dev(mspmv_handle a, mspmv_ic0 m, int transpose, con
     if (!a->d_ctrl)
         ST_TRY(dev_alloc(&a->d_ctrl, 1));
     HIP_TRY(hipMemsetAsync(a->d_ctrl, 0, sizeof(CgControl), a->stream));
-    HIP_TRY(launch_ic0_trsv(m, transpose == 0, d_B, d_X, L, a->d_ctrl, a->stream));
+    HIP_TRY(launch_ic0_trsv(m, which == 0, d_B, d_X, L, a->d_ctrl, a->stream));
     HIP_TRY(hipStreamSynchronize(a->stream));
     CgControl fin{};
     HIP_TRY(hipMemcpy(&fin, a->d_ctrl, sizeof(CgControl), hipMemcpyDeviceToHost));
     if (fin.breakdown == 2) {
-        set_error("IC(0) solve: a triangular-solve dependency never became ready (solve stalled)");
+        set_error(std::string(what) + " solve: a triangular-solve dependency never became ready (solve stalled)");
         return MSPMV_ERR_STALL;
     }
     return MSPMV_OK;
+}
+
+mspmv_status mspmv_ic0_solve_dev(mspmv_handle a, mspmv_ic0 m, int transpose, const double *d_B, double *d_X, int L)
+{
+    return tri_solve_dev(a, m, transpose, d_B, d_X, L, "IC(0)", "transpose must be 0 (L X = B) or 1 (L^T X = B)");
+}
+
+// ---- ILU(0) factor on the device --------------------------------------------------------------
+mspmv_status mspmv_ilu0_create(const mspmv_csr_d *lu, int device, mspmv_ilu0 *out)
+{
+    if (!out)
+        return invalid("null output");
+    *out = nullptr;
+    ST_TRY(ilu0_check_rows(lu, "ilu0_create"));
+    const int n = lu->num_rows, nnz = lu->num_nonzeros;
+    const int *ro = lu->row_offsets, *ci = lu->column_indices;
+    // L: the strictly lower entries, then a stored 1.0 diagonal (k_trsv_tagged finds a diagonal by j == i and
+    // divides by it: by 1.0, exactly); U: the diagonal first, then the upper entries.  A solve divides by U's
+    // diagonal: zero or non-finite is refused here.
+    std::vector<int> lro((size_t)n + 1, 0), uro((size_t)n + 1, 0);
+    std::vector<int> lci, uci;
+    std::vector<double> lva, uva;
+    lci.reserve((size_t)nnz + 1), lva.reserve((size_t)nnz + 1), uci.reserve((size_t)nnz + 1), uva.reserve((size_t)nnz + 1);
+    for (int i = 0; i < n; ++i) {
+        for (int k = ro[i]; k < ro[i + 1]; ++k) {
+            const double v = lu->values[k];
+            if (ci[k] < i) {
+                lci.push_back(ci[k]), lva.push_back(v);
+            } else {
+                if (ci[k] == i && (v == 0.0 || !std::isfinite(v)))
+                    return invalid("ILU(0) factor row " + std::to_string(i) + " has a zero or non-finite diagonal");
+                uci.push_back(ci[k]), uva.push_back(v);
+            }
+        }
+        lci.push_back(i), lva.push_back(1.0);
+        lro[(size_t)i + 1] = (int)lci.size();
+        uro[(size_t)i + 1] = (int)uci.size();
+    }
+    mspmv_ilu0_s *m = new mspmv_ilu0_s;
+    const mspmv_status st = upload_triangles(n, lro.data(), lci.data(), lva.data(), (int)lci.size(), uro.data(),
+                                             uci.data(), uva.data(), (int)uci.size(), device, &m->tri, "ILU(0)");
+    if (st != MSPMV_OK) {
+        mspmv_ilu0_destroy(m);
+        return st;
+    }
+    *out = m;
+    return MSPMV_OK;
+}
+
+mspmv_status mspmv_ilu0_destroy(mspmv_ilu0 m)
+{
+    if (!m)
+        return MSPMV_OK;
+    ic0_release(&m->tri);
+    dev_free(m->d_hat);
+    delete m;
+    return MSPMV_OK;
+}
+
+mspmv_status mspmv_ilu0_solve_dev(mspmv_handle a, mspmv_ilu0 m, int upper, const double *d_B, double *d_X, int L)
+{
+    return tri_solve_dev(a, m ? &m->tri : nullptr, upper, d_B, d_X, L, "ILU(0)",
+                         "upper must be 0 (L X = B) or 1 (U X = B)");
 }
 
 // ---- measurement ---------------------------------------------------------------------------

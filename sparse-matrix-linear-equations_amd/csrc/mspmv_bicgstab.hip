@@ -11,6 +11,12 @@
 // (mspmv_device.h).  Breakdown is per column, as in the split CG: a non-finite alpha, omega or beta freezes the
 // column (kConvBroken: alpha = omega = beta = 0 from then on, X and R keep their last finite values, left out
 // of the history) and the other columns keep iterating.
+// Right-preconditioned with an ILU(0) factor M = L U (mspmv_dpbicgstab_ilu0_multi; launch_pbicgstab_iteration):
+//     Phat = U^-1 L^-1 P;  V = A Phat;  ...  X += alpha Phat;  Shat = U^-1 L^-1 s;  T = A Shat;  ...  X += omega Shat
+// and everything else as above: R is the original system's residual, so the stop test and the history mean the
+// same.  Four sync-free triangular solves per iteration (launch_ic0_trsv: L into the factor's intermediate, U
+// into the factor's hat panel, which Phat and then Shat share), and the s and update passes in their PRE
+// instantiation, which take X's direction from the hat panel; the other three passes are shared.
 // Compiled with -ffp-contract=off like every kernel here: every a*b+c is two roundings.
 #include "mspmv_internal.h"
 #include "mspmv_device.h"
@@ -27,6 +33,7 @@ struct BicgArgs {
     double *p;
     double *v;          // A p
     double *t;          // A s
+    const double *hat;  // preconditioned only: Phat in the s pass, Shat in the update pass
     const double *b;    // init only
     CgScalars *scal;
     CgControl *ctrl;
@@ -40,6 +47,13 @@ struct BicgArgs {
 };
 
 __device__ __forceinline__ bool bicg_finite(double a) { return a == a && fabs(a) < HUGE_VAL; }
+
+// A column froze: MSPMV_ERR_BREAKDOWN, unless a triangular-solve stall (2: MSPMV_ERR_STALL) is on record.
+__device__ __forceinline__ void bicg_note_freeze(CgControl *ctrl)
+{
+    if (ctrl->breakdown != 2)
+        ctrl->breakdown = 1;
+}
 
 // {f(j), f(j + 1)} for the column pair (j, j + 1) this thread meets in every chunk of a pass (for_pairs); L == 1:
 // f(0) twice, the pair being two rows of the one column.
@@ -182,7 +196,7 @@ __global__ __launch_bounds__(kBlock) void k_bicg_dot(BicgArgs a)
             al = s.rho / d;
             if (!bicg_finite(al)) {  // rho = 0 (a zero right-hand side: 0/0) or rhat.V = 0
                 a.conv[tid] = kConvBroken;
-                a.ctrl->breakdown = 1;
+                bicg_note_freeze(a.ctrl);
                 al = 0.0;
             }
         }
@@ -193,20 +207,22 @@ __global__ __launch_bounds__(kBlock) void k_bicg_dot(BicgArgs a)
     bicg_stop_if_none_live<L>(a);
 }
 
-// s = R - alpha V in R's storage, X += alpha P; every block forms the masked alpha from rho / red.
-template <int L>
+// s = R - alpha V in R's storage, X += alpha P (PRE: alpha Phat); every block forms the masked alpha from
+// rho / red.
+template <int L, bool PRE>
 __global__ __launch_bounds__(kBlock) void k_bicg_s(BicgArgs a)
 {
     constexpr int GL = L > 1 ? L / 2 : 1;
     if (a.ctrl->done)
         return;
+    const double *dir = PRE ? a.hat : a.p;
     const double2 al = bicg_col_pair<L>([&](int j) {
         const double q = a.conv[j] ? 0.0 : a.scal[j].rho / a.red[j];
         return bicg_finite(q) ? q : 0.0;
     });
     for_pairs<GL>(a.n_elems / 2, 0, [&](long long i) {
         const double2 v = reinterpret_cast<const double2 *>(a.v)[i];
-        const double2 p = reinterpret_cast<const double2 *>(a.p)[i];
+        const double2 p = reinterpret_cast<const double2 *>(dir)[i];
         double2 r = reinterpret_cast<double2 *>(a.r)[i];
         double2 x = reinterpret_cast<double2 *>(a.x)[i];
         r.x = r.x - al.x * v.x;
@@ -219,7 +235,7 @@ __global__ __launch_bounds__(kBlock) void k_bicg_s(BicgArgs a)
     if ((a.n_elems & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
         const long long i = a.n_elems - 1;
         a.r[i] = a.r[i] - al.x * a.v[i];
-        a.x[i] = a.x[i] + al.x * a.p[i];
+        a.x[i] = a.x[i] + al.x * dir[i];
     }
 }
 
@@ -259,7 +275,7 @@ __global__ __launch_bounds__(kBlock) void k_bicg_tdots(BicgArgs a)
             om = s_out[L + tid] / d;
             if (!bicg_finite(om)) {  // x keeps alpha p, r keeps s
                 a.conv[tid] = kConvBroken;
-                a.ctrl->breakdown = 1;
+                bicg_note_freeze(a.ctrl);
                 om = 0.0;
             }
         }
@@ -269,10 +285,10 @@ __global__ __launch_bounds__(kBlock) void k_bicg_tdots(BicgArgs a)
     bicg_stop_if_none_live<L>(a);
 }
 
-// X += omega s, R = s - omega T, with R.R and rhat.R from the same sweep as one fold of 2 L values.  The last
-// block: convergence masks, the history entry, the stop test, beta and rho (a non-finite beta -- rho = 0 or
-// omega = 0 on a column still iterating -- freezes the column), the iteration counter.
-template <int L>
+// X += omega s (PRE: omega Shat), R = s - omega T, with R.R and rhat.R from the same sweep as one fold of 2 L
+// values.  The last block: convergence masks, the history entry, the stop test, beta and rho (a non-finite
+// beta -- rho = 0 or omega = 0 on a column still iterating -- freezes the column), the iteration counter.
+template <int L, bool PRE>
 __global__ __launch_bounds__(kBlock) void k_bicg_update(BicgArgs a)
 {
     constexpr int GL = L > 1 ? L / 2 : 1;
@@ -290,8 +306,14 @@ __global__ __launch_bounds__(kBlock) void k_bicg_update(BicgArgs a)
         const double2 h = reinterpret_cast<const double2 *>(a.rhat)[i];
         double2 r = reinterpret_cast<double2 *>(a.r)[i];
         double2 x = reinterpret_cast<double2 *>(a.x)[i];
-        x.x = x.x + om.x * r.x;
-        x.y = x.y + om.y * r.y;
+        if (PRE) {
+            const double2 sh = reinterpret_cast<const double2 *>(a.hat)[i];
+            x.x = x.x + om.x * sh.x;
+            x.y = x.y + om.y * sh.y;
+        } else {
+            x.x = x.x + om.x * r.x;
+            x.y = x.y + om.y * r.y;
+        }
         r.x = r.x - om.x * t.x;
         r.y = r.y - om.y * t.y;
         reinterpret_cast<double2 *>(a.x)[i] = x;
@@ -304,7 +326,7 @@ __global__ __launch_bounds__(kBlock) void k_bicg_update(BicgArgs a)
     if ((a.n_elems & 1) && blockIdx.x == 0 && tid == 0) {
         const long long i = a.n_elems - 1;
         const double s = a.r[i];
-        a.x[i] = a.x[i] + om.x * s;
+        a.x[i] = a.x[i] + om.x * (PRE ? a.hat[i] : s);
         const double r = s - om.x * a.t[i];
         a.r[i] = r;
         rr.x += r * r;
@@ -345,7 +367,7 @@ __global__ __launch_bounds__(kBlock) void k_bicg_update(BicgArgs a)
                     ++live;
                 } else {
                     a.conv[j] = kConvBroken;
-                    a.ctrl->breakdown = 1;
+                    bicg_note_freeze(a.ctrl);
                     be = 0.0;
                 }
             }
@@ -428,14 +450,53 @@ hipError_t launch_bicgstab_iteration(mspmv_handle_s *h, const TilePlan &plan, co
         constexpr int LL = decltype(Lc)::value;
         const dim3 grid(nblk), block(kBlock);
         hipLaunchKernelGGL((k_bicg_dot<LL>), grid, block, 0, h->stream, a);
-        hipLaunchKernelGGL((k_bicg_s<LL>), grid, block, 0, h->stream, a);
+        hipLaunchKernelGGL((k_bicg_s<LL, false>), grid, block, 0, h->stream, a);
         hipError_t el = hipGetLastError();
         if (el != hipSuccess)
             return el;
         if ((el = launch_solver_product(h, plan, splan, h->d_r, h->d_p1, L)) != hipSuccess)  // T = A s
             return el;
         hipLaunchKernelGGL((k_bicg_tdots<LL>), grid, block, 0, h->stream, a);
-        hipLaunchKernelGGL((k_bicg_update<LL>), grid, block, 0, h->stream, a);
+        hipLaunchKernelGGL((k_bicg_update<LL, false>), grid, block, 0, h->stream, a);
+        hipLaunchKernelGGL((k_bicg_p<LL>), grid, block, 0, h->stream, a);
+        return hipGetLastError();
+    });
+}
+
+// dst = U^-1 L^-1 src through the factor's intermediate; every solve's output is a panel of its own (the
+// pending-pattern fill overwrites it first).
+static hipError_t ilu0_apply(mspmv_handle_s *h, mspmv_ilu0_s *ilu, int L, const double *src, double *dst)
+{
+    hipError_t e = launch_ic0_trsv(&ilu->tri, true, src, ilu->tri.d_y, L, h->d_ctrl, h->stream);
+    if (e == hipSuccess)
+        e = launch_ic0_trsv(&ilu->tri, false, ilu->tri.d_y, dst, L, h->d_ctrl, h->stream);
+    return e;
+}
+
+hipError_t launch_pbicgstab_iteration(mspmv_handle_s *h, mspmv_ilu0_s *ilu, const TilePlan &plan,
+                                      const TilePlan *splan, double *d_x, int L, int nblk, double tol)
+{
+    BicgArgs a = bicg_args(h, d_x, L, tol);
+    a.hat = ilu->d_hat;
+    hipError_t e = ilu0_apply(h, ilu, L, h->d_p0, ilu->d_hat);  // Phat
+    if (e != hipSuccess)
+        return e;
+    if ((e = launch_solver_product(h, plan, splan, ilu->d_hat, h->d_ap, L)) != hipSuccess)  // V = A Phat
+        return e;
+    return dispatch_L(L, [&](auto Lc) {
+        constexpr int LL = decltype(Lc)::value;
+        const dim3 grid(nblk), block(kBlock);
+        hipLaunchKernelGGL((k_bicg_dot<LL>), grid, block, 0, h->stream, a);
+        hipLaunchKernelGGL((k_bicg_s<LL, true>), grid, block, 0, h->stream, a);
+        hipError_t el = hipGetLastError();
+        if (el != hipSuccess)
+            return el;
+        if ((el = ilu0_apply(h, ilu, L, h->d_r, ilu->d_hat)) != hipSuccess)  // Shat (Phat is dead)
+            return el;
+        if ((el = launch_solver_product(h, plan, splan, ilu->d_hat, h->d_p1, L)) != hipSuccess)  // T = A Shat
+            return el;
+        hipLaunchKernelGGL((k_bicg_tdots<LL>), grid, block, 0, h->stream, a);
+        hipLaunchKernelGGL((k_bicg_update<LL, true>), grid, block, 0, h->stream, a);
         hipLaunchKernelGGL((k_bicg_p<LL>), grid, block, 0, h->stream, a);
         return hipGetLastError();
     });

@@ -293,6 +293,10 @@ struct mspmv_handle_s {
     hipGraph_t bicg_graph = nullptr;
     hipGraphExec_t bicg_exec = nullptr;
     std::vector<const void *> bicg_graph_key;
+    // ... and the ILU(0)-preconditioned BiCGSTAB's (pbicgstab_solve_native): the same workspace, other launches
+    hipGraph_t pbicg_graph = nullptr;
+    hipGraphExec_t pbicg_exec = nullptr;
+    std::vector<const void *> pbicg_graph_key;
     // timing
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double last_tile_kernel_ms = 0.0;
@@ -355,7 +359,21 @@ struct mspmv_ic0_s {
     size_t y_cap = 0;
 };
 
+// ILU(0) factor on the device (mspmv_ilu0_create): two different triangles in mspmv_ic0_s's slots -- L (A's
+// strictly lower entries, then an explicit 1.0 diagonal, so k_trsv_tagged divides by 1.0 exactly) where IC(0)
+// keeps its L, and U (diagonal first) where IC(0) keeps L^T -- so launch_ic0_trsv runs unchanged; tri.d_y is
+// the intermediate of an apply.  A type of its own: a nonsymmetric factor is no argument of the PCG.
+struct mspmv_ilu0_s {
+    mspmv_ic0_s tri;
+    double *d_hat = nullptr;  // [n * L] Phat, then Shat, of the running iteration (mspmv_bicgstab.hip)
+    size_t hat_cap = 0;
+};
+
 namespace mspmv {
+
+// Square, consistent CSR whose rows ascend strictly and hold their diagonal (mspmv_ilu0.cpp); else
+// MSPMV_ERR_INVALID, the message (prefixed with who) naming the first offending row.
+mspmv_status ilu0_check_rows(const mspmv_csr_d *a, const char *who);
 
 // ---- column-slab SpMV (mspmv_slab.hip) ---------------------------------------------
 constexpr int kSlabPlanKey = -1;
@@ -521,6 +539,10 @@ hipError_t launch_solver_product(mspmv_handle_s *h, const TilePlan &plan, const 
 hipError_t launch_bicgstab_init(mspmv_handle_s *h, const double *d_b, double *d_x, int L, double tol, int nblk);
 hipError_t launch_bicgstab_iteration(mspmv_handle_s *h, const TilePlan &plan, const TilePlan *splan, double *d_x, int L,
                                      int nblk, double tol);
+// The same right-preconditioned with M = L U (ilu: the factor): Phat = U^-1 L^-1 P before the first product,
+// Shat = U^-1 L^-1 s before the second (both in ilu->d_hat, through ilu->tri.d_y), X advanced along them.
+hipError_t launch_pbicgstab_iteration(mspmv_handle_s *h, mspmv_ilu0_s *ilu, const TilePlan &plan,
+                                      const TilePlan *splan, double *d_x, int L, int nblk, double tol);
 // Iterations per CG batch / graph replay for an m-row, nnz-nonzero matrix and L columns (mspmv_api.hip).
 int cg_batch_iters(long long m, long long nnz, int L);
 // Pipelined single-RHS CG (L == 1 unless MSPMV_CG_SPLIT=1): init (x = 0, r = p0 = b, b.b

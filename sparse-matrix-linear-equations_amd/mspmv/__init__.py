@@ -111,6 +111,12 @@ _SIGS = {
     "mspmv_dpcg_ic0_multi": (_I, [_P, _P, _P, _P, _I, _I, _D, _I, _PI, _P, _I]),
     "mspmv_dpcg_ic0_multi_dev": (_I, [_P, _P, _P, _P, _I, _I, _D, _I, _PI, _P, _I]),
     "mspmv_ic0_solve_dev": (_I, [_P, _P, _I, _P, _P, _I]),
+    "mspmv_ilu0_values": (_I, [ctypes.POINTER(_CsrD), _P]),
+    "mspmv_ilu0_create": (_I, [ctypes.POINTER(_CsrD), _I, ctypes.POINTER(_P)]),
+    "mspmv_ilu0_destroy": (_I, [_P]),
+    "mspmv_ilu0_solve_dev": (_I, [_P, _P, _I, _P, _P, _I]),
+    "mspmv_dpbicgstab_ilu0_multi": (_I, [_P, _P, _P, _P, _I, _I, _D, _PI, _P, _I]),
+    "mspmv_dpbicgstab_ilu0_multi_dev": (_I, [_P, _P, _P, _P, _I, _I, _D, _PI, _P, _I]),
     "mspmv_dpcg_spai_multi": (_I, [_P, _P, _P, _P, _I, _I, _D, _I, _PI, _P, _I]),
     "mspmv_dpcg_spai_multi_dev": (_I, [_P, _P, _P, _P, _I, _I, _D, _I, _PI, _P, _I]),
     "mspmv_time_spmm_dev": (_I, [_P, _P, _P, _I, _I, _SZ, _PD]),
@@ -750,6 +756,92 @@ def pcg_ic0(g: "GpuCsr", ic: GpuIc0, B: np.ndarray, max_iters: int, tolerance: f
     return X, it.value, hist[: min(it.value, hist_cap)], st
 
 
+def ilu0_values(a: CsrMatrix) -> np.ndarray:
+    """ILU(0) of A in A's own pattern (mspmv_ilu0_values; host, IKJ order): the factors' values in A's CSR
+    order -- column < row: L's multipliers (unit diagonal implied), column >= row: U.  A zero or non-finite
+    pivot raises MspmvError(4); there is no diagonal shifting."""
+    out = np.zeros(max(a.num_nonzeros, 1), np.float64)
+    _check(lib.mspmv_ilu0_values(ctypes.byref(a._c()), _ptr(out)), "ilu0_values")
+    return out[: a.num_nonzeros]
+
+
+class GpuIlu0:
+    """An ILU(0) factor (L with unit diagonal, and U) resident on a device for the GPU triangular solves.
+    `lu`: A's pattern with ilu0_values(A)."""
+
+    def __init__(self, lu: CsrMatrix, device: int = 0):
+        h = ctypes.c_void_p()
+        _check(lib.mspmv_ilu0_create(ctypes.byref(lu._c()), device, ctypes.byref(h)), "ilu0_create")
+        self.h = h.value
+        self.device = device
+        _track(self)
+
+    def solve_dev(self, g: "GpuCsr", dB: "DeviceBuffer", dX: "DeviceBuffer", L: int, upper: bool = False) -> int:
+        """mspmv_ilu0_solve_dev on device panels: one triangular solve, L X = B or U X = B."""
+        return _check(lib.mspmv_ilu0_solve_dev(g.h, self.h, int(bool(upper)), dB.ptr, dX.ptr, L), "ilu0_solve_dev")
+
+    def solve(self, g: "GpuCsr", B: np.ndarray, upper: bool = False) -> np.ndarray:
+        """One triangular solve with the factor on g's stream (mspmv_ilu0_solve_dev): X with L X = B, or
+        U X = B (upper), for a host panel B [n] or [n, L], L in SUPPORTED_L."""
+        B = np.ascontiguousarray(B, np.float64)
+        shape = B.shape
+        if B.ndim == 1:
+            B = B[:, None]
+        dB = DeviceBuffer.from_array(B, self.device) if B.size else DeviceBuffer(16, self.device)
+        dX = DeviceBuffer(max(B.nbytes, 16), self.device)
+        try:
+            self.solve_dev(g, dB, dX, B.shape[1], upper)
+            return dX.download(B.shape).reshape(shape)
+        finally:
+            dB.free()
+            dX.free()
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib.mspmv_ilu0_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def pbicgstab_ilu0(g: "GpuCsr", m: GpuIlu0, B: np.ndarray, max_iters: int, tolerance: float, hist_cap: int = 0,
+                   allow_fault: bool = False):
+    """ILU(0)-preconditioned multi-RHS BiCGSTAB (mspmv_dpbicgstab_ilu0_multi): (X, iterations, history,
+    status); a per-column breakdown is returned, not raised, as GpuCsr.bicgstab's."""
+    B = np.ascontiguousarray(B, np.float64)
+    if B.ndim == 1:
+        B = B[:, None]
+    L = B.shape[1]
+    X = np.empty_like(B)
+    it = ctypes.c_int()
+    hist = np.zeros(max(hist_cap, 1), np.float64)
+    st = lib.mspmv_dpbicgstab_ilu0_multi(g.h, m.h, _ptr(B), _ptr(X), L, max_iters, tolerance, ctypes.byref(it),
+                                         _ptr(hist) if hist_cap else None, hist_cap)
+    _check(st, "dpbicgstab_ilu0_multi", allow=(4, FAULT) if allow_fault else (4,))
+    return X, it.value, hist[: min(it.value, hist_cap)], st
+
+
+def pbicgstab_ilu0_dev(g: "GpuCsr", m: GpuIlu0, dB: DeviceBuffer, dX: DeviceBuffer, L: int, max_iters: int,
+                       tolerance: float, hist_cap: int = 0):
+    """mspmv_dpbicgstab_ilu0_multi_dev on device panels: (iterations, history, status)."""
+    it = ctypes.c_int()
+    hist = np.zeros(max(hist_cap, 1), np.float64)
+    st = lib.mspmv_dpbicgstab_ilu0_multi_dev(g.h, m.h, dB.ptr, dX.ptr, L, max_iters, tolerance, ctypes.byref(it),
+                                             _ptr(hist) if hist_cap else None, hist_cap)
+    _check(st, "dpbicgstab_ilu0_multi_dev", allow=(4,))
+    return it.value, hist[: min(it.value, hist_cap)], st
+
+
 def offset_windows(a: CsrMatrix, min_fill: float = 0.85, min_window_fill: float = 0.3):
     """Host-side offset-window planning (mspmv_offset_windows; no device): None when the matrix does
     not fit the plan, else {"windows", "sum_offsets", "masked_windows", "k", "remainder"} (k: offsets
@@ -871,6 +963,26 @@ def BiCGStabSolveMultiple(a: CsrMatrix, B, X, num_vectors: int, max_iters: int, 
     cap = max_iters if max_errors is not None else 0
     Xs, it, hist, st = _gpu(a).bicgstab(Bm, max_iters, tolerance, hist_cap=cap)
     _note_breakdown(st, "BiCGStabSolveMultiple")
+    X[:] = Xs.reshape(-1)
+    if max_errors is not None:
+        max_errors.clear()
+        max_errors.extend(hist.tolist())
+    return it
+
+
+def ILU0BiCGStabSolveMultiple(a: CsrMatrix, B, X, num_vectors: int, max_iters: int, tolerance: float,
+                              max_errors: Optional[list] = None) -> int:
+    """ILU(0)-preconditioned multi-RHS BiCGSTAB in BiCGStabSolveMultiple's calling form (no reference
+    counterpart); the factor is computed on the first call and cached on the matrix object, as
+    PCGSolveMultiple caches its device factor.  Returns the iteration count."""
+    Bm = np.asarray(B, np.float64).reshape(a.num_rows, num_vectors)
+    cap = max_iters if max_errors is not None else 0
+    m = getattr(a, "_gpu_ilu0", None)
+    if m is None or m.h is None:
+        m = GpuIlu0(CsrMatrix.from_arrays(a.num_cols, a.row_offsets, a.column_indices, ilu0_values(a)))
+        object.__setattr__(a, "_gpu_ilu0", m)
+    Xs, it, hist, st = pbicgstab_ilu0(_gpu(a), m, Bm, max_iters, tolerance, hist_cap=cap)
+    _note_breakdown(st, "ILU0BiCGStabSolveMultiple")
     X[:] = Xs.reshape(-1)
     if max_errors is not None:
         max_errors.clear()

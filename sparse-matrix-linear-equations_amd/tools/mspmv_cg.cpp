@@ -7,9 +7,12 @@
 //
 //   --solver=bicgstab: the same two legs on mspmv_dbicgstab_multi (nonsymmetric matrices; the single leg
 //     solves its vectors one after another at L = 1).  Default --solver=cg.
+//   --precond=ilu0 (with --solver=bicgstab only): mspmv_dpbicgstab_ilu0_multi, the ILU(0) factor computed and
+//     uploaded once before the timed solves, its time on a line of its own.  Default --precond=none.
 //
 //   mspmv_cg --mtx=<file> [--multi] [--num_vectors=16] [--max_iters=N] [--tolerance=1e-5]
 //            [--timing_iters=1] [--output=<csv>] [--seed=42] [--device=0] [--quiet] [--solver=cg|bicgstab]
+//            [--precond=none|ilu0]
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -78,6 +81,17 @@ int main(int argc, char **argv)
         return 1;
     }
     const bool bicg = solver == "bicgstab";
+    std::string precond = "none";
+    arg(argc, argv, "precond", precond);
+    if (precond != "none" && precond != "ilu0") {
+        fprintf(stderr, "--precond must be none or ilu0\n");
+        return 1;
+    }
+    const bool ilu = precond == "ilu0";
+    if (ilu && !bicg) {
+        fprintf(stderr, "--precond=ilu0 needs --solver=bicgstab\n");
+        return 1;
+    }
     if (mtx.empty()) {
         fprintf(stderr, "Usage: %s --mtx=<filename> [--multi] [options]\n", argv[0]);
         return 1;
@@ -91,6 +105,18 @@ int main(int argc, char **argv)
     mspmv_handle h = nullptr;
     if ((st = mspmv_csr_create(&a, device, &h)) != MSPMV_OK)
         die("mspmv_csr_create", st);
+    mspmv_ilu0 pre = nullptr;
+    if (ilu) {  // setup, outside the solve timing
+        const auto f0 = std::chrono::steady_clock::now();
+        std::vector<double> lu((size_t)std::max(nnz, 1));
+        if ((st = mspmv_ilu0_values(&a, lu.data())) != MSPMV_OK)
+            die("mspmv_ilu0_values", st);
+        const mspmv_csr_d f{m, n, nnz, ro, ci, lu.data()};
+        if ((st = mspmv_ilu0_create(&f, device, &pre)) != MSPMV_OK)
+            die("mspmv_ilu0_create", st);
+        printf("ILU(0) factorisation: %.3f ms\n",
+               std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - f0).count());
+    }
     // RHS: srand(seed); B[i] = rand()/RAND_MAX over n*L (cpu_singlecg.cpp:87-90)
     std::vector<double> B((size_t)m * L), X((size_t)m * L);
     srand(seed);
@@ -100,8 +126,15 @@ int main(int argc, char **argv)
     for (int i = 0; i < m; ++i)
         nb += B[i] * B[i];
     const double threshold = std::sqrt(nb) * tol;  // calculate_threshold, cpu_singlecg.cpp:22-34
-    // per iteration and column: CG one product and 10 vector flops per row; BiCGSTAB two products and 22
-    const double flops1 = bicg ? 4.0 * nnz + 22.0 * m : 2.0 * nnz + 10.0 * m;
+    // the BiCGSTAB legs' solve, plain or preconditioned
+    auto bicgstab = [&](const double *b, double *x, int w, int *it, double *h_out, int cap) {
+        return ilu ? mspmv_dpbicgstab_ilu0_multi(h, pre, b, x, w, max_iters, threshold, it, h_out, cap)
+                   : mspmv_dbicgstab_multi(h, b, x, w, max_iters, threshold, it, h_out, cap);
+    };
+    const char *bicg_name = ilu ? "mspmv_dpbicgstab_ilu0_multi" : "mspmv_dbicgstab_multi";
+    // per iteration and column: CG one product and 10 vector flops per row; BiCGSTAB two products and 22, and
+    // with ILU(0) four triangular solves over the factors' nnz + m entries (the stored unit diagonal included)
+    const double flops1 = bicg ? 4.0 * nnz + 22.0 * m + (ilu ? 4.0 * (nnz + (double)m) : 0.0) : 2.0 * nnz + 10.0 * m;
     const std::string name = base_name(mtx);
     double min_ms = std::numeric_limits<double>::max();
     long long iters_min = 0;
@@ -112,21 +145,19 @@ int main(int argc, char **argv)
         if (!multi) {
             for (int v = 0; v < L; ++v) {  // column blocks B[v*n .. ] (single_strategy.hpp:219-226)
                 int it = 0;
-                st = bicg ? mspmv_dbicgstab_multi(h, &B[(size_t)v * m], &X[(size_t)v * m], 1, max_iters, threshold, &it,
-                                                  nullptr, 0)
+                st = bicg ? bicgstab(&B[(size_t)v * m], &X[(size_t)v * m], 1, &it, nullptr, 0)
                           : mspmv_dcg_single(h, &B[(size_t)v * m], &X[(size_t)v * m], max_iters, threshold, &it, nullptr, 0);
                 if (st != MSPMV_OK && st != MSPMV_ERR_BREAKDOWN)
-                    die(bicg ? "mspmv_dbicgstab_multi" : "mspmv_dcg_single", st);
+                    die(bicg ? bicg_name : "mspmv_dcg_single", st);
                 total += it;
             }
         } else {
             int it = 0;
-            st = bicg ? mspmv_dbicgstab_multi(h, B.data(), X.data(), L, max_iters, threshold, &it,
-                                              t == 0 ? hist.data() : nullptr, t == 0 ? max_iters : 0)
+            st = bicg ? bicgstab(B.data(), X.data(), L, &it, t == 0 ? hist.data() : nullptr, t == 0 ? max_iters : 0)
                       : mspmv_dcg_multi(h, B.data(), X.data(), L, max_iters, threshold, MSPMV_NONZERO_SPLIT, &it,
                                         t == 0 ? hist.data() : nullptr, t == 0 ? max_iters : 0);
             if (st != MSPMV_OK && st != MSPMV_ERR_BREAKDOWN)
-                die(bicg ? "mspmv_dbicgstab_multi" : "mspmv_dcg_multi", st);
+                die(bicg ? bicg_name : "mspmv_dcg_multi", st);
             total = it;
             if (t == 0)
                 hist.resize(std::min<size_t>(hist.size(), (size_t)it));
@@ -139,7 +170,7 @@ int main(int argc, char **argv)
             iters_min = total;
         }
     }
-    const char *method = bicg ? "GPU_BICGSTAB_LOOP" : "GPU_SINGLE_LOOP";
+    const char *method = ilu ? "GPU_ILU0_BICGSTAB_LOOP" : bicg ? "GPU_BICGSTAB_LOOP" : "GPU_SINGLE_LOOP";
     if (!multi) {
         const double gflops = flops1 * (double)iters_min / (min_ms / 1000.0) / 1e9;
         printf("    %s, L=%d, method=%s: %.3f ms, %lld iters, %.2f GFLOPS\n", name.c_str(), L, method, min_ms,
@@ -167,6 +198,7 @@ int main(int argc, char **argv)
             fprintf(stderr, "Error: Cannot open file %s for writing\n", out_csv.c_str());
         }
     }
+    mspmv_ilu0_destroy(pre);
     mspmv_destroy(h);
     mspmv_host_free(ro);
     mspmv_host_free(ci);
