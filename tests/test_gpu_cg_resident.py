@@ -5,6 +5,10 @@ against the pipelined two-kernel path (MSPMV_CG_RESIDENT=0) on the same inputs.
 
 Tolerances as tests/test_gpu_cg.py (north_star "CG residual match within 1e-10 rel"): iteration
 counts equal, every ||r_k||/||b|| within 1e-10, x within 1e-8 relative.
+
+The stencils here reach two of the kernel's nine (rows per thread, slots per row) shapes;
+test_gpu_cg_resident_shapes.py runs every shape, in both forms, on matrices with unequal rows,
+scattered columns, unequal and empty row blocks (resident_cases.py), with solve() and FORMS from here.
 """
 import os
 
