@@ -426,6 +426,14 @@ MSPMV_API const char *mspmv_spmm_kernel_name(mspmv_handle h, int L);
  * matrix register/LDS-resident on every CU, one cooperative launch per solve), "pipelined (...)"
  * (single RHS, two kernels per iteration), or the split multi-RHS / PCG forms.  "" before any. */
 MSPMV_API const char *mspmv_cg_kernel_name(mspmv_handle h);
+/* The kernel instantiation the two products of the last BiCGSTAB / ILU(0)-BiCGSTAB solve on this handle ran, in
+ * rocprofv3's spelling: "k_spmm_dia<L,nt>" (offset windows), "k_spmm_slab<cfg,nt>" (column slabs, L = 8 / 16),
+ * "k_spmm_blk<L,0,nt,KR>" (node blocks), "k_spmm_tile<L,ipt,0,nt,dict,carries>" (merge tiles; carries: rows split
+ * across tiles), and for L = 1 off the windows "k_spmv_tile<...>" / "k_spmv_blk<...>".  It is the solver's own
+ * choice, which mspmv_spmm_kernel_name does not report: a solver never multiplies on the plain SpMV's one-wave,
+ * sliced-ELL or run-balanced plans.  For a width outside 1, 2, 4, 8, 16 it names the last column group's kernel.
+ * "" before any such solve.  Read-only: it changes no launch.  Valid until the next solve on the handle. */
+MSPMV_API const char *mspmv_solver_product_kernel_name(mspmv_handle h);
 
 /* ---- fault detection ----------------------------------------------------------------- */
 /* The kernels' cross-workgroup folds (CG dot products, rows split between tiles, column groups) are

@@ -1026,6 +1026,8 @@ const char *mspmv_last_error(void) { return g_err.c_str(); }
 
 const char *mspmv_cg_kernel_name(mspmv_handle h) { return h ? h->last_cg_kernel.c_str() : ""; }
 
+const char *mspmv_solver_product_kernel_name(mspmv_handle h) { return h ? h->last_solver_product.c_str() : ""; }
+
 const char *mspmv_spmv_kernel_name(mspmv_handle h)
 {
     thread_local std::string name;
@@ -2075,6 +2077,7 @@ static mspmv_status bicgstab_solve_native(mspmv_handle_s *h, const double *d_b, 
         ST_TRY(ilu0_workspace(ilu, elems));
     const char *name = ilu ? "ILU0-BiCGSTAB" : "BiCGSTAB";
     h->last_cg_kernel = ilu ? "ILU0-BiCGSTAB (2 SpMM + 4 trsv + 5 passes)" : "BiCGSTAB (2 SpMM + 5 passes)";
+    h->last_solver_product = solver_product_kernel_name(h, *plan, splan, L);
     const int use_cap = hist ? cap : 0;
     const int saved_cap = h->hist_cap;
     h->hist_cap = use_cap;  // kernels record only what the caller asked for

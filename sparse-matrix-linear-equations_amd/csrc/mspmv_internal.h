@@ -305,6 +305,8 @@ struct mspmv_handle_s {
     size_t flush_cap = 0;
     mspmv::ResidentCg *rcg = nullptr;  // register-resident CG layout (built on the first single-RHS CG)
     std::string last_cg_kernel;        // the CG path the last solve ran (mspmv_cg_kernel_name)
+    // the kernel the last BiCGSTAB solve's two products ran (mspmv_solver_product_kernel_name)
+    std::string last_solver_product;
     // plain single-RHS SpMV on one-wave tiles (a plan of its own, TilePlan::lanes = 64): -1 not
     // decided yet, 0 no, 1 yes (mspmv_api.hip spmv_plan: skewed rows, most tiles merge walks)
     int spmv_onewave = -1;
@@ -486,6 +488,8 @@ int spmv_tile_blocks_per_cu();
 hipError_t launch_stream_read(const double *p, size_t bytes, int num_cus, hipStream_t s);
 std::string spmv_kernel_name(const mspmv_handle_s *h);
 std::string spmm_kernel_name(const mspmv_handle_s *h, const TilePlan &plan, int L);
+// the kernel launch_solver_product launches on (plan, splan) at native width L
+std::string solver_product_kernel_name(const mspmv_handle_s *h, const TilePlan &plan, const TilePlan *splan, int L);
 bool stream_nt(const mspmv_handle_s *h);
 
 // ---- runtime -> template dispatch ---------------------------------------------------

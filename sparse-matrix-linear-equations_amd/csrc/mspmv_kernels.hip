@@ -2353,6 +2353,34 @@ std::string spmm_kernel_name(const mspmv_handle_s *h, const TilePlan &plan, int 
            (dict ? ",true,true>" : plan.num_carries > 0 ? ",false,true>" : ",false,false>");
 }
 
+// The kernel launch_solver_product launches for a solve's two products of native width L on (plan, splan),
+// spelled as rocprofv3 lists it: launch_solver_product -> launch_spmm_tile_only -> launch_tile<kModeSpmv>,
+// restated.  Unlike spmm_kernel_name it never names the plain SpMV's own plans (one-wave tiles, sliced ELL,
+// run-balanced node blocks), which no solver multiplies on.
+std::string solver_product_kernel_name(const mspmv_handle_s *h, const TilePlan &plan, const TilePlan *splan, int L)
+{
+    if (splan && splan->dia)
+        return dia_kernel_name(h, L);
+    if (splan && splan->slab)
+        return slab_mm_kernel_name(h, *splan);
+    const std::string nt = stream_nt(h) ? "true" : "false";
+    const bool fix = plan.num_carries > 0;  // make_args: TileArgs::fix
+    const bool all_reg = plan.d_blk && plan.num_tiles_reg == plan.num_tiles && (L == 1 || spmm_blk_enabled());
+    if (L == 1) {  // launch_spmv_1<kModeSpmv>
+        if (plan.blk_spmv)
+            return "k_spmv_blk<0," + nt + (all_reg ? ",6,false>" : ",6,true>");
+        const std::string head = "k_spmv_tile<" + std::to_string(kSpmvIpt) + ",0," + nt;
+        if (plan.lanes == 64)
+            return head + ",64,true,true>";
+        return head + ",256,true," + (fix ? "true>" : "false>");
+    }
+    if (all_reg)  // launch_spmm_L
+        return "k_spmm_blk<" + std::to_string(L) + ",0," + nt + "," + std::to_string(blk_kr(plan)) + ">";
+    const bool dict = spmm_dict_max(L) > 0 && plan.d_dict;
+    return "k_spmm_tile<" + std::to_string(L) + "," + std::to_string(spmm_iptg_for(L)) + ",0," + nt +
+           (dict ? ",true,true>" : fix ? ",false,true>" : ",false,false>");
+}
+
 // Resident workgroups per CU of a kBlock-thread kernel from its own resources on gfx950: 160 KiB
 // of LDS per CU, 512 VGPRs per SIMD lane (granule 8), at most 8 waves per SIMD, 4 SIMDs.
 static int gfx950_blocks_per_cu(const void *fn)

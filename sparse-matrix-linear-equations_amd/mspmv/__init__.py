@@ -135,6 +135,7 @@ _SIGS = {
     "mspmv_spmv_kernel_name": (ctypes.c_char_p, [_P]),
     "mspmv_spmm_kernel_name": (ctypes.c_char_p, [_P, _I]),
     "mspmv_cg_kernel_name": (ctypes.c_char_p, [_P]),
+    "mspmv_solver_product_kernel_name": (ctypes.c_char_p, [_P]),
     "mspmv_device_malloc": (_I, [_I, _SZ, ctypes.POINTER(_P)]),
     "mspmv_device_free": (_I, [_P]),
     "mspmv_memcpy_h2d": (_I, [_P, _P, _SZ]),
@@ -540,6 +541,11 @@ class GpuCsr:
     def cg_kernel_name(self) -> str:
         """The CG path the last solve on this matrix ran (mspmv_cg_kernel_name)."""
         return lib.mspmv_cg_kernel_name(self.h).decode()
+
+    def solver_product_kernel_name(self) -> str:
+        """The kernel the last BiCGSTAB / ILU(0)-BiCGSTAB solve's two products ran
+        (mspmv_solver_product_kernel_name)."""
+        return lib.mspmv_solver_product_kernel_name(self.h).decode()
 
     def cg_resident_stamps(self, db: "DeviceBuffer", dx: "DeviceBuffer", max_iters: int, tolerance: float,
                            stamp_iters: int):

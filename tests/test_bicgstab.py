@@ -94,7 +94,19 @@ def rhs(n, L):
 def csr_mm(a, X):
     """A X by segment sums (every row of the test matrices holds its diagonal: no empty rows)."""
     ro, ci, va = a
-    return np.add.reduceat(va[:, None] * X[ci], ro[:-1].astype(np.int64), axis=0)
+    ro = ro.astype(np.int64)
+    n = len(ro) - 1
+    if len(ci) * X.shape[1] <= 1 << 17:
+        return np.add.reduceat(va[:, None] * X[ci], ro[:-1], axis=0)
+    # the same sums, a block of whole rows (about 8,192 entries) at a time: the products stay in cache
+    out = np.empty((n, X.shape[1]), np.result_type(va, X))
+    r = 0
+    while r < n:
+        e = min(max(int(np.searchsorted(ro, ro[r] + 8192, side="right")) - 1, r + 1), n)
+        s0, s1 = ro[r], ro[e]
+        out[r:e] = np.add.reduceat(va[s0:s1, None] * X[ci[s0:s1]], ro[r:e] - s0, axis=0)
+        r = e
+    return out
 
 
 # ---- the dot product's summation order ----------------------------------------------------------
@@ -185,6 +197,12 @@ def true_residual(a, B, X):
 
 @functools.lru_cache(maxsize=None)
 def matrix(name):
+    """(row_offsets, column_indices, values); built once per session, do not modify.  The names of
+    bicgstab_cases.py are registered here too, so that reference(), test_ilu0.factor() and apply_plans() take them."""
+    import bicgstab_cases
+
+    if name in bicgstab_cases.NAMES:
+        return bicgstab_cases.build(name)
     return {"convdiff30": lambda: convdiff(30, 31), "convdiff60": lambda: convdiff(60, 47), "randdd": randdd}[name]()
 
 
@@ -199,7 +217,7 @@ def reference(name, L, max_iters=200):
 
 # ---- what the GPU tests rely on ----------------------------------------------------------------
 CASES = [("convdiff30", 1), ("convdiff30", 8), ("convdiff60", 1), ("convdiff60", 8), ("randdd", 1), ("randdd", 8),
-         ("randdd", 6)]
+         ("randdd", 6), ("convdiff30", 4), ("randdd", 4)]
 COUNT_RANGE = {"convdiff30": (46, 50), "convdiff60": (69, 70), "randdd": (11, 13)}
 
 

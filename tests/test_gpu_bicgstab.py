@@ -60,7 +60,7 @@ def check_history(name, hist, ref):
     assert np.all(err <= bar), np.max(err / bar)
 
 
-@pytest.mark.parametrize("L", [1, 2, 8, 6, 16])
+@pytest.mark.parametrize("L", [1, 2, 4, 8, 6, 16])
 @pytest.mark.parametrize("name", ["convdiff30", "randdd"])
 def test_against_restatement(mspmv, name, L):
     a = tb.matrix(name)
@@ -109,9 +109,8 @@ def test_default_plan_offset_windows(mspmv, monkeypatch, L):
     ref = tb.reference("convdiff60", L)
     with mspmv.GpuCsr(csr(mspmv, a), device=0) as g:
         X, it, hist, st = g.bicgstab(B, MAX_ITERS, TOL, hist_cap=MAX_ITERS)
-        kernel = g.spmm_kernel_name(L)
-    if "k_spmm_dia" not in kernel:
-        pytest.skip(f"the plain L = {L} product of this matrix does not take the offset windows ({kernel})")
+        kernel = g.solver_product_kernel_name()
+    assert kernel.startswith(f"k_spmm_dia<{L},"), kernel
     assert st == 0
     check_counts(it, ref)
     check_true_residual(a, B, X)

@@ -151,7 +151,7 @@ def test_solve_argument_checks(mspmv):
 
 
 # ---- the solver --------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("L", [1, 2, 8, 6, 16])
+@pytest.mark.parametrize("L", [1, 2, 4, 8, 6, 16])
 @pytest.mark.parametrize("name", ["convdiff30", "randdd"])
 def test_against_restatement(mspmv, name, L):
     a = ti.matrix(name)
@@ -200,9 +200,8 @@ def test_default_plan_offset_windows(mspmv, monkeypatch, L):
     ref = ti.reference("convdiff60", L)
     with Solver(mspmv, "convdiff60") as s:
         X, it, hist, st = s.solve(B)
-        kernel = s.g.spmm_kernel_name(L)
-    if "k_spmm_dia" not in kernel:
-        pytest.skip(f"the plain L = {L} product of this matrix does not take the offset windows ({kernel})")
+        kernel = s.g.solver_product_kernel_name()
+    assert kernel.startswith(f"k_spmm_dia<{L},"), kernel
     assert st == 0
     check_counts(it, ref)
     check_true_residual(a, B, X)

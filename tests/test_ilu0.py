@@ -396,7 +396,7 @@ def test_ilu0_create_rejects_a_diagonal_no_solve_may_divide_by(bad):
 
 
 # The issue's table: iterations to TOL at L = 1 / 8, unpreconditioned and with ILU(0).
-CASES = [(name, L) for name in ("convdiff30", "convdiff60", "randdd", "convdiff60s") for L in (1, 8, 6)]
+CASES = [(name, L) for name in ("convdiff30", "convdiff60", "randdd", "convdiff60s") for L in (1, 8, 6, 4)]
 COUNTS = {("convdiff30", 1): 11, ("convdiff30", 8): 11, ("convdiff60", 1): 12, ("convdiff60", 8): 13,
           ("randdd", 1): 5, ("randdd", 8): 6, ("convdiff60s", 1): 6, ("convdiff60s", 8): 7}
 
