@@ -1902,6 +1902,24 @@ static mspmv_status cg_solve_native(mspmv_handle_s *h, const double *d_b, double
         return MSPMV_ERR_STALL;
     }
     if (fin.breakdown) {
+        if (!pipelined && fin.done && fin.iters_out == fin.iter + 1 && hist && it >= 1 && it <= use_cap) {
+            // The alpha test ended the solve (cg_alpha_finish: every column not yet converged broke down in
+            // this iteration's p.Ap), so the update that records the iteration's history entry never ran and
+            // the slot held what an earlier solve left there.  The entry is the reference's: the largest of
+            // the converged columns' residuals, frozen since they converged -- a broken column's NaN is
+            // skipped by its std::max -- and 0 when no column has converged.
+            std::vector<CgScalars> sc((size_t)L);
+            std::vector<unsigned char> cv((size_t)L);
+            HIP_TRY(hipMemcpy(sc.data(), h->d_scal, sizeof(CgScalars) * (size_t)L, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(cv.data(), h->d_conv, (size_t)L, hipMemcpyDeviceToHost));
+            double maxrel = 0.0;
+            for (int j = 0; j < L; ++j)
+                if (cv[(size_t)j] == 1) {
+                    const double rel = std::sqrt(sc[(size_t)j].rs_new) / sc[(size_t)j].b_norm;
+                    maxrel = maxrel < rel ? rel : maxrel;
+                }
+            hist[it - 1] = maxrel;
+        }
         set_error(L == 1 ? "CG breakdown: p.Ap gave a non-finite alpha at iteration " + std::to_string(it)
                          : "CG breakdown: p.Ap gave a non-finite alpha in at least one column (frozen; the "
                            "other columns were solved)");
