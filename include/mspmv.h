@@ -299,6 +299,48 @@ MSPMV_API mspmv_status mspmv_ilu0_destroy(mspmv_ilu0 m);
  * untouched on a rejected call. */
 MSPMV_API mspmv_status mspmv_ilu0_solve_dev(mspmv_handle a, mspmv_ilu0 m, int upper, const double *d_B,
                                             double *d_X, int L);
+
+/* ---- multi-colour ILU(0): the factor whose solves are one parallel sweep per colour ------- */
+/* Greedy colouring of the graph of A + A^T's off-diagonal pattern (stored zeros count as entries):
+ * rows 0..n-1 in turn take the smallest colour that no already-coloured neighbour holds.  Sequential
+ * and deterministic.  colors[n] receives the colours, *num_colors their number, at most the largest
+ * degree of the symmetrised pattern + 1.  A must pass mspmv_ilu0_values' row checks
+ * (MSPMV_ERR_INVALID otherwise). */
+MSPMV_API mspmv_status mspmv_color_greedy(const mspmv_csr_d *a, int *colors, int *num_colors);
+/* Ap = P A P^T for a square CSR A: row i of Ap is row perm[i] of A, its columns renumbered by the
+ * inverse permutation and sorted ascending.  ro[n + 1], ci[nnz], va[nnz] receive Ap.
+ * MSPMV_ERR_INVALID when perm is not a permutation of 0..n-1 (an index out of range or repeated). */
+MSPMV_API mspmv_status mspmv_csr_permute_sym(const mspmv_csr_d *a, const int *perm, int *ro, int *ci, double *va);
+/* The multi-colour ILU(0) factor of A itself (not of a factor): rows that share a colour share no
+ * entry, perm orders the rows stably by colour (ascending within a colour), and the factor is
+ * mspmv_ilu0_values run on Ap = P A P^T, so it has at most as many dependency levels as colours and
+ * a triangular solve is one launch per colour.  colors == NULL: mspmv_color_greedy's.  Colours the
+ * caller supplies (a block or any other colouring) must lie in [0, n), use every colour of 0..C-1,
+ * and give no two rows joined by an entry (i, j), i != j, of A the same colour: MSPMV_ERR_INVALID
+ * otherwise, the message naming the first offending row.  A's row checks are mspmv_ilu0_values';
+ * a zero or non-finite pivot of the permuted factorisation is MSPMV_ERR_BREAKDOWN (the row named in
+ * the colour ordering).  All of that happens before the device is touched.  Uploaded: L's strictly
+ * lower entries (unit diagonal implied), U with the diagonal first, perm and the colour offsets.
+ * The result is an ordinary mspmv_ilu0: mspmv_dpbicgstab_ilu0_multi[_dev] takes it unchanged
+ * (mspmv_cg_kernel_name then reads "MC-ILU0-BiCGSTAB (2 SpMM + 4 sweeps of C colours + 5 passes)"
+ * and MSPMV_ERR_STALL cannot occur), mspmv_ilu0_destroy frees it.
+ * Summation order of a solve's row: the first product plus numpy's pairwise sum of the rest (in
+ * CSR order; sequential up to 7 further products, eight interleaved running sums beyond, halves
+ * beyond 128) -- the order np.add.reduceat gives, so a solve is reproducible against it bit for
+ * bit.  A long row is summed by max(1, L / 2) lanes alone: the known cost of that exactness. */
+MSPMV_API mspmv_status mspmv_ilu0_create_colored(const mspmv_csr_d *a, const int *colors, int device,
+                                                 mspmv_ilu0 *out);
+/* *num_colors: the factor's colours, 0 for a natural-order factor (mspmv_ilu0_create); perm (null,
+ * or n entries): row i of the permuted matrix is row perm[i] of A (untouched for 0 colours).
+ * On a multi-colour factor mspmv_ilu0_solve_dev solves one triangle of Ap's factor, B and X in the
+ * colour ordering, under the same argument contract. */
+MSPMV_API mspmv_status mspmv_ilu0_colors(mspmv_ilu0 m, int *num_colors, int *perm);
+/* X = M^-1 B = U^-1 L^-1 B in A's own ordering, for either kind of factor, on a's stream,
+ * synchronised: the two tagged solves through the factor's intermediate (natural order), or the
+ * colour sweeps, which gather by perm on the way in and scatter on the way out (no pass of their
+ * own).  mspmv_ilu0_solve_dev's argument contract without `upper`; X is untouched on a rejected
+ * call. */
+MSPMV_API mspmv_status mspmv_ilu0_apply_dev(mspmv_handle a, mspmv_ilu0 m, const double *d_B, double *d_X, int L);
 /* Right-preconditioned multi-RHS BiCGSTAB with M = L U.  The residual is the original system's, so
  * the stop test and the history mean what they mean in mspmv_dbicgstab_multi.  Per column, X = 0,
  * R = Rhat = P = B, rho = B.B; per iteration Phat = U^-1 L^-1 P, V = A Phat, alpha = rho / (Rhat.V),

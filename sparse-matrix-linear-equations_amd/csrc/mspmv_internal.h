@@ -365,13 +365,36 @@ struct mspmv_ic0_s {
 // strictly lower entries, then an explicit 1.0 diagonal, so k_trsv_tagged divides by 1.0 exactly) where IC(0)
 // keeps its L, and U (diagonal first) where IC(0) keeps L^T -- so launch_ic0_trsv runs unchanged; tri.d_y is
 // the intermediate of an apply.  A type of its own: a nonsymmetric factor is no argument of the PCG.
+// A multi-colour factor (mspmv_ilu0_create_colored) is the ILU(0) of Ap = P A P^T in the same slots, rows of a
+// colour contiguous: L without its unit diagonal, U diagonal first (the level orders upload_triangles builds are
+// not used); colour c's rows are [color_off[c], color_off[c + 1]), row i of Ap is row perm[i] of A.  Its solves
+// are one k_trsv_color launch per colour (mspmv_color.hip), never k_trsv_tagged.
 struct mspmv_ilu0_s {
     mspmv_ic0_s tri;
     double *d_hat = nullptr;  // [n * L] Phat, then Shat, of the running iteration (mspmv_bicgstab.hip)
     size_t hat_cap = 0;
+    int num_colors = 0;       // 0: a natural-order factor
+    std::vector<int> color_off, perm;
+    std::vector<int> lmax, umax;  // [C] the longest row of the colour, in off-diagonal entries, of L and of U
+    int *d_perm = nullptr;
 };
 
 namespace mspmv {
+
+// The host side of mspmv_ilu0_create_colored (mspmv_color.cpp): the checks, the ordering and the factor of the
+// permuted matrix, split into L (strictly lower) and U (diagonal first).
+mspmv_status ilu0_colored_host(const mspmv_csr_d *a, const int *colors, std::vector<int> &perm,
+                               std::vector<int> &color_off, std::vector<int> &lro, std::vector<int> &lci,
+                               std::vector<double> &lva, std::vector<int> &uro, std::vector<int> &uci,
+                               std::vector<double> &uva);
+// One triangle of a multi-colour factor, in the colour ordering: X = L^-1 B (colours ascending) or U^-1 B
+// (descending), one launch per colour on s.  B and X are distinct panels.
+hipError_t launch_color_trsv(const mspmv_ilu0_s *ilu, bool upper, const double *d_b, double *d_x, int L,
+                             const CgControl *ctrl, hipStream_t s);
+// dst = P^T U^-1 L^-1 P src, in A's own ordering, through tri.d_y (n x L): the forward sweeps gather src by perm
+// into d_y, the backward sweeps run in place on d_y and scatter into dst; 2 C launches.
+hipError_t launch_color_apply(const mspmv_ilu0_s *ilu, const double *d_src, double *d_dst, int L,
+                              const CgControl *ctrl, hipStream_t s);
 
 // Square, consistent CSR whose rows ascend strictly and hold their diagonal (mspmv_ilu0.cpp); else
 // MSPMV_ERR_INVALID, the message (prefixed with who) naming the first offending row.

@@ -115,6 +115,11 @@ _SIGS = {
     "mspmv_ilu0_create": (_I, [ctypes.POINTER(_CsrD), _I, ctypes.POINTER(_P)]),
     "mspmv_ilu0_destroy": (_I, [_P]),
     "mspmv_ilu0_solve_dev": (_I, [_P, _P, _I, _P, _P, _I]),
+    "mspmv_color_greedy": (_I, [ctypes.POINTER(_CsrD), _P, _PI]),
+    "mspmv_csr_permute_sym": (_I, [ctypes.POINTER(_CsrD), _P, _P, _P, _P]),
+    "mspmv_ilu0_create_colored": (_I, [ctypes.POINTER(_CsrD), _P, _I, ctypes.POINTER(_P)]),
+    "mspmv_ilu0_colors": (_I, [_P, _PI, _P]),
+    "mspmv_ilu0_apply_dev": (_I, [_P, _P, _P, _P, _I]),
     "mspmv_dpbicgstab_ilu0_multi": (_I, [_P, _P, _P, _P, _I, _I, _D, _PI, _P, _I]),
     "mspmv_dpbicgstab_ilu0_multi_dev": (_I, [_P, _P, _P, _P, _I, _I, _D, _PI, _P, _I]),
     "mspmv_dpcg_spai_multi": (_I, [_P, _P, _P, _P, _I, _I, _D, _I, _PI, _P, _I]),
@@ -771,9 +776,33 @@ def ilu0_values(a: CsrMatrix) -> np.ndarray:
     return out[: a.num_nonzeros]
 
 
+def color_greedy(a: CsrMatrix):
+    """Greedy colouring of A + A^T's off-diagonal pattern (mspmv_color_greedy; host): (colors [n] int32,
+    num_colors).  Rows 0..n-1 in turn take the smallest colour no already-coloured neighbour holds."""
+    colors = np.zeros(max(a.num_rows, 1), np.int32)
+    num = ctypes.c_int()
+    _check(lib.mspmv_color_greedy(ctypes.byref(a._c()), _ptr(colors), ctypes.byref(num)), "color_greedy")
+    return colors[: a.num_rows], num.value
+
+
+def csr_permute_sym(a: CsrMatrix, perm) -> CsrMatrix:
+    """P A P^T (mspmv_csr_permute_sym; host): row i of the result is row perm[i] of A, columns renumbered by
+    the inverse permutation and ascending."""
+    perm = np.ascontiguousarray(perm, np.int32)
+    if perm.shape != (a.num_rows,):
+        raise ValueError("perm must hold one index per row")
+    ro = np.zeros(a.num_rows + 1, np.int32)
+    ci = np.zeros(max(a.num_nonzeros, 1), np.int32)
+    va = np.zeros(max(a.num_nonzeros, 1), np.float64)
+    _check(lib.mspmv_csr_permute_sym(ctypes.byref(a._c()), _ptr(perm), _ptr(ro), _ptr(ci), _ptr(va)),
+           "csr_permute_sym")
+    return CsrMatrix.from_arrays(a.num_cols, ro, ci[: a.num_nonzeros], va[: a.num_nonzeros])
+
+
 class GpuIlu0:
     """An ILU(0) factor (L with unit diagonal, and U) resident on a device for the GPU triangular solves.
-    `lu`: A's pattern with ilu0_values(A)."""
+    `lu`: A's pattern with ilu0_values(A).  GpuIlu0.colored(A) builds the multi-colour factor of A itself,
+    whose solves are one parallel sweep per colour."""
 
     def __init__(self, lu: CsrMatrix, device: int = 0):
         h = ctypes.c_void_p()
@@ -782,13 +811,70 @@ class GpuIlu0:
         self.device = device
         _track(self)
 
+    @classmethod
+    def colored(cls, a: CsrMatrix, colors=None, device: int = 0) -> "GpuIlu0":
+        """The multi-colour ILU(0) factor of A (mspmv_ilu0_create_colored): `colors` [n] (None: color_greedy's)
+        orders the rows colour after colour, and the factor is ILU(0) of the permuted matrix.  Every check and
+        the factorisation run on the host before the device is touched."""
+        if colors is not None:
+            colors = np.ascontiguousarray(colors, np.int32)
+            if colors.shape != (a.num_rows,):
+                raise ValueError("colors must hold one colour per row")
+        h = ctypes.c_void_p()
+        _check(lib.mspmv_ilu0_create_colored(ctypes.byref(a._c()), None if colors is None else _ptr(colors), device,
+                                             ctypes.byref(h)), "ilu0_create_colored")
+        self = cls.__new__(cls)
+        self.h = h.value
+        self.device = device
+        self.num_rows = a.num_rows
+        _track(self)
+        return self
+
+    @property
+    def num_colors(self) -> int:
+        """The factor's colours; 0 for a natural-order factor."""
+        num = ctypes.c_int()
+        _check(lib.mspmv_ilu0_colors(self.h, ctypes.byref(num), None), "ilu0_colors")
+        return num.value
+
+    @property
+    def perm(self):
+        """Row i of the permuted matrix is row perm[i] of A (int32 [n]); None for a natural-order factor."""
+        if self.num_colors == 0:
+            return None
+        num = ctypes.c_int()
+        perm = np.zeros(max(self.num_rows, 1), np.int32)
+        _check(lib.mspmv_ilu0_colors(self.h, ctypes.byref(num), _ptr(perm)), "ilu0_colors")
+        return perm[: self.num_rows]
+
+    def apply_dev(self, g: "GpuCsr", dB: "DeviceBuffer", dX: "DeviceBuffer", L: int) -> int:
+        """mspmv_ilu0_apply_dev on device panels: X = U^-1 L^-1 B in A's own ordering."""
+        return _check(lib.mspmv_ilu0_apply_dev(g.h, self.h, dB.ptr, dX.ptr, L), "ilu0_apply_dev")
+
+    def apply(self, g: "GpuCsr", B: np.ndarray) -> np.ndarray:
+        """The preconditioner apply X = M^-1 B on g's stream (mspmv_ilu0_apply_dev), for either kind of factor:
+        a host panel B [n] or [n, L], L in SUPPORTED_L, in A's own ordering."""
+        B = np.ascontiguousarray(B, np.float64)
+        shape = B.shape
+        if B.ndim == 1:
+            B = B[:, None]
+        dB = DeviceBuffer.from_array(B, self.device) if B.size else DeviceBuffer(16, self.device)
+        dX = DeviceBuffer(max(B.nbytes, 16), self.device)
+        try:
+            self.apply_dev(g, dB, dX, B.shape[1])
+            return dX.download(B.shape).reshape(shape)
+        finally:
+            dB.free()
+            dX.free()
+
     def solve_dev(self, g: "GpuCsr", dB: "DeviceBuffer", dX: "DeviceBuffer", L: int, upper: bool = False) -> int:
         """mspmv_ilu0_solve_dev on device panels: one triangular solve, L X = B or U X = B."""
         return _check(lib.mspmv_ilu0_solve_dev(g.h, self.h, int(bool(upper)), dB.ptr, dX.ptr, L), "ilu0_solve_dev")
 
     def solve(self, g: "GpuCsr", B: np.ndarray, upper: bool = False) -> np.ndarray:
         """One triangular solve with the factor on g's stream (mspmv_ilu0_solve_dev): X with L X = B, or
-        U X = B (upper), for a host panel B [n] or [n, L], L in SUPPORTED_L."""
+        U X = B (upper), for a host panel B [n] or [n, L], L in SUPPORTED_L.  On a multi-colour factor the
+        triangle is the permuted matrix's, B and X in the colour ordering."""
         B = np.ascontiguousarray(B, np.float64)
         shape = B.shape
         if B.ndim == 1:

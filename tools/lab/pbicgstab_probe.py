@@ -5,11 +5,14 @@ iteration of each, one JSON line per (width, solver).  Warm runs (plans, workspa
 a first solve), then the median of `reps` solves.  Both calls return after their stream has drained, so a solve
 is timed by the host clock around the call: launches past convergence and the last control-word copy are
 included, as in bicgstab_probe.py.
-    pbicgstab_probe.py [nx ny [L ...]] [--reps=5] [--c=0.4] [--d=0.3]      default 2000 2000 1 16
+    pbicgstab_probe.py [nx ny [L ...]] [--reps=5] [--c=0.4] [--d=0.3] [--colored]      default 2000 2000 1 16
+--colored adds the multi-colour ILU(0) factor (mspmv_ilu0_create_colored, greedy colours: one parallel sweep per
+colour instead of a dependency chain) as a third solver, "colored", beside "plain" and "ilu0".
 The share of an iteration spent in the triangular solves comes from a kernel trace of this script:
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o p -- python pbicgstab_probe.py ... --only=ilu0
     pbicgstab_probe.py --stats=DIR/.../p_kernel_stats.csv
-prints the summed duration per kernel family (k_trsv_tagged, the products, the k_bicg_* passes, the fills).
+prints the summed duration per kernel family (k_trsv_tagged, the colour sweeps k_trsv_color, the products, the
+k_bicg_* passes, the fills).
 MSPMV_LIB selects the library; MSPMV_DIA=0 keeps the products on the merge tiles."""
 import csv
 import json
@@ -30,11 +33,12 @@ TOL = 1e-9
 
 def kernel_shares(path):
     """Summed duration per kernel family from rocprofv3's *_kernel_stats.csv."""
-    fam = {"trsv": 0.0, "product": 0.0, "passes": 0.0, "fill": 0.0, "other": 0.0}
+    fam = {"trsv": 0.0, "sweep": 0.0, "product": 0.0, "passes": 0.0, "fill": 0.0, "other": 0.0}
     with open(path, newline="") as f:
         for row in csv.DictReader(f):
             name, ns = row["Name"], float(row["TotalDurationNs"])
-            key = ("trsv" if "k_trsv_tagged" in name else "passes" if "k_bicg_" in name else
+            key = ("trsv" if "k_trsv_tagged" in name else "sweep" if "k_trsv_color" in name else
+                   "passes" if "k_bicg_" in name else
                    "product" if any(k in name for k in ("k_spmm", "k_spmv", "k_dia", "k_slab")) else
                    "fill" if "fill" in name.lower() or "memset" in name.lower() else "other")
             fam[key] += ns
@@ -44,7 +48,7 @@ def kernel_shares(path):
 
 
 def main():
-    opts = dict(a[2:].split("=", 1) for a in sys.argv[1:] if a.startswith("--"))
+    opts = dict(a[2:].split("=", 1) for a in sys.argv[1:] if a.startswith("--") and "=" in a)
     if "stats" in opts:
         return kernel_shares(opts["stats"])
     args = [int(v) for v in sys.argv[1:] if not v.startswith("--")]
@@ -57,9 +61,14 @@ def main():
     t0 = time.perf_counter()
     lu = mspmv.CsrMatrix.from_arrays(n, a.row_offsets, a.column_indices, mspmv.ilu0_values(a))
     factor_ms = (time.perf_counter() - t0) * 1e3
+    t0 = time.perf_counter()
+    mc = mspmv.GpuIlu0.colored(a) if "--colored" in sys.argv[1:] else None  # colouring, ordering, factor, upload
+    colored_ms = (time.perf_counter() - t0) * 1e3
     with mspmv.GpuCsr(a) as g, mspmv.GpuIlu0(lu) as m:
         solvers = {"plain": lambda dB, dX, L: g.bicgstab_dev(dB, dX, L, 100000, TOL),
                    "ilu0": lambda dB, dX, L: mspmv.pbicgstab_ilu0_dev(g, m, dB, dX, L, 100000, TOL)}
+        if mc is not None:
+            solvers["colored"] = lambda dB, dX, L: mspmv.pbicgstab_ilu0_dev(g, mc, dB, dX, L, 100000, TOL)
         for L in widths:
             B = np.random.default_rng(7 + L).uniform(0, 1, (n, L))
             dB, dX = mspmv.DeviceBuffer.from_array(B), mspmv.DeviceBuffer(8 * n * L)
@@ -81,10 +90,14 @@ def main():
                                   "status": st, "iterations": it, "reps": reps,
                                   "ms_per_solve": round(med * 1e3, 3), "ms_per_iter": round(med * 1e3 / max(it, 1), 4),
                                   "min_ms_per_solve": round(min(times) * 1e3, 3), "true_residual": res,
-                                  "host_factor_ms": round(factor_ms, 1), "product": g.spmm_kernel_name(L),
+                                  "host_factor_ms": round(colored_ms if name == "colored" else factor_ms, 1),
+                                  "colors": mc.num_colors if name == "colored" else 0,
+                                  "product": g.spmm_kernel_name(L),
                                   "kernel": g.cg_kernel_name()}), flush=True)
             dB.free()
             dX.free()
+    if mc is not None:
+        mc.close()
 
 
 if __name__ == "__main__":
