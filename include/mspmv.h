@@ -418,6 +418,9 @@ MSPMV_API mspmv_status mspmv_plan_dict_tiles(mspmv_handle h, int L, int *tiles_d
  * LDS slots and reduction (bit-identical to it).  Tiles that hold whole rows only, <= 16 run
  * chunks, mean run height >= ~1.7 (others: 0). */
 MSPMV_API mspmv_status mspmv_plan_block_tiles(mspmv_handle h, int L, int *tiles_blk);
+/* Of those, the tiles with more than 8 run chunks (*tiles_two_rounds): the column-pair kernel takes
+ * them in a second round of its eight half-wave run slots. */
+MSPMV_API mspmv_status mspmv_plan_block_rounds(mspmv_handle h, int L, int *tiles_two_rounds);
 /* Each tile's in-tile reduction for L right-hand sides (num_tiles entries; 255 = a node-block
  * tile summed in registers by a fixed lane tree, see mspmv_plan_block_tiles): 0 = merge walk
  * (one walker per thread, or per L/2 lanes), g > 0 = row groups with 2^(g-1) nonzero-parallel

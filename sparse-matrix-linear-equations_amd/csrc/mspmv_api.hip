@@ -101,6 +101,7 @@ static void free_plan(TilePlan &p)
     dev_free(p.d_ndict);
     dev_free(p.d_idx16);
     dev_free(p.d_blk);
+    dev_free(p.d_pcols);
     free_slab(p.slab);
     p.slab = nullptr;
     free_dia(p.dia);
@@ -500,7 +501,7 @@ static mspmv_status build_plan(mspmv_handle_s *h, int L, const TilePlan **out, i
         p.d_blk = nullptr;
         p.blk_rows_max = maxh > 0 ? maxh : 8;
         if (p.num_tiles_blk > 0) {  // repack at the smallest stride that holds every tile's set
-            p.blk_stride = maxnd <= 16 ? 16 : maxnd <= 32 ? 32 : 64;
+            p.blk_stride = maxnd <= 8 ? 8 : maxnd <= 16 ? 16 : maxnd <= 32 ? 32 : 64;
             std::vector<uint4> packed((size_t)T * p.blk_stride, make_uint4(0u, 0u, 0u, 0u));
             for (int t = 0; t < T; ++t)
                 for (int i = 0, nd = (int)((hd[(size_t)t * kBlkPerTile].y >> 8) & 255u); i < nd; ++i)
@@ -509,6 +510,20 @@ static mspmv_status build_plan(mspmv_handle_s *h, int L, const TilePlan **out, i
                 return fail(st);
             if (hipMemcpy(p.d_blk, packed.data(), sizeof(uint4) * packed.size(), hipMemcpyHostToDevice) != hipSuccess) {
                 set_error("node blocks: upload failed");
+                return fail(MSPMV_ERR_HIP);
+            }
+            // the chunks' pattern columns once more, one 128-B slot per descriptor slot (hipMalloc aligns
+            // the array to more than a line): the kernels read a run's columns there, not in cols16
+            const size_t np = packed.size() * 64;
+            if ((st = dev_alloc(&p.d_pcols, np)) != MSPMV_OK)
+                return fail(st);
+            e = hipMemsetAsync(p.d_pcols, 0, sizeof(unsigned short) * np, h->stream);
+            if (e == hipSuccess)
+                e = launch_fill_pcols(p.d_blk, p.blk_stride, p.d_bounds, p.d_cols16, T, p.d_pcols, h->stream);
+            if (e == hipSuccess)
+                e = hipStreamSynchronize(h->stream);
+            if (e != hipSuccess) {
+                set_error(std::string("node blocks: pattern-column slots: ") + hipGetErrorString(e));
                 return fail(MSPMV_ERR_HIP);
             }
         }
@@ -3110,6 +3125,19 @@ mspmv_status mspmv_plan_block_tiles(mspmv_handle h, int L, int *tiles_blk)
     const TilePlan *plan = nullptr;
     ST_TRY(get_plan(h, L, &plan, true));
     *tiles_blk = plan->d_blk ? plan->num_tiles_blk : 0;
+    return MSPMV_OK;
+}
+
+mspmv_status mspmv_plan_block_rounds(mspmv_handle h, int L, int *tiles_two_rounds)
+{
+    ST_TRY(check_handle(h));
+    if (!tiles_two_rounds)
+        return invalid("null out pointer");
+    if (!supported_L(L))
+        return (set_error("L must be one of 1, 2, 4, 8, 16"), MSPMV_ERR_UNSUPPORTED);
+    const TilePlan *plan = nullptr;
+    ST_TRY(get_plan(h, L, &plan, true));
+    *tiles_two_rounds = plan->d_blk ? plan->blk_two_rounds : 0;
     return MSPMV_OK;
 }
 

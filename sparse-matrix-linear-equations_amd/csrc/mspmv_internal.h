@@ -177,10 +177,15 @@ struct TilePlan {
     int *d_ndict = nullptr;             // [num_tiles]
     unsigned short *d_idx16 = nullptr;  // [nnz + kNnzPad]
     int num_tiles_dict = 0;             // tiles that gather through their dictionary
-    // Single-RHS plans: node-block run descriptors (k_build_blocks), blk_stride (16, 32 or 64) per
+    // Single-RHS plans: node-block run descriptors (k_build_blocks), blk_stride (8, 16, 32 or 64) per
     // tile, entry 0 of a tile holding its count (0: striped staging).  Null when no tile qualifies.
     uint4 *d_blk = nullptr;             // [num_tiles * blk_stride]
     int blk_stride = 0;
+    // ... and the chunks' pattern columns, one 128-B line per descriptor slot: slot (t, di) at
+    // ((size_t)t * blk_stride + di) * 64 holds chunk di's wc 16-bit column offsets (those of cols16, same
+    // colbase[t]), positions wc .. 63 repeating the last one; slots without a chunk are zero, so every
+    // position names a column of the tile's range.  A slot's address needs no descriptor.
+    unsigned short *d_pcols = nullptr;  // [num_tiles * blk_stride * 64]
     int num_tiles_blk = 0;              // tiles staged by node blocks
     int num_tiles_reg = 0;              // of those, tiles reduced in registers (h_blk_reg)
     int blk_rows_max = 8;               // the tallest run (rows of one node) over the descriptors
@@ -479,6 +484,9 @@ constexpr int kBlkTileChunks = 8;
 hipError_t launch_build_blocks(const int *d_row_offsets, const int *d_cols, const int2 *d_bounds,
                                const unsigned char *d_split, const int *d_colbase, int num_tiles, uint4 *d_blk,
                                hipStream_t s, int max_chunks = 8);
+// TilePlan::d_pcols (zeroed by the caller) from the repacked descriptors and cols16.
+hipError_t launch_fill_pcols(const uint4 *d_blk, int blk_stride, const int2 *d_bounds,
+                             const unsigned short *d_cols16, int num_tiles, unsigned short *d_pcols, hipStream_t s);
 hipError_t launch_build_dict(const int *d_cols, const int2 *d_bounds, int num_tiles, int max_items, int *d_dict,
                              int *d_ndict, unsigned short *d_idx16, hipStream_t s, bool multi, int L = 1);
 // Multi-RHS column dictionaries: the distinct panel rows a tile parks in LDS, 8 KB per workgroup

@@ -296,13 +296,14 @@ __global__ __launch_bounds__(kBlock) void k_build_dict(const int *__restrict__ c
 // and every result bit -- is unchanged.
 //
 // Descriptor of one run chunk (16 B; at most kBlkMax per tile, tile t's at blk[t * stride ..], the
-// plan's stride being the smallest of 16, 32, 64 that holds every tile's set):
+// plan's stride being the smallest of 8, 16, 32, 64 that holds every tile's set; the chunk's pattern
+// columns sit once more in a 128-B slot of their own, k_fill_pcols, which is where the kernels read them):
 //   x: vofs (nonzero offset of the run's first row in the tile, bits 0-15) | j0 (first pattern
 //      column of this chunk, 16-23) | wc (chunk width <= 64, 24-31)
 //   y: h (rows, 1..8, bits 0-3) | p (row holding P, 4-6) | nd (descriptor count, in entry 0 only,
 //      8-15; 0 = the tile stages the plain way) | rofs (the run's first row in the tile, 16-31)
 //   z, w: the h row lengths, 8 bits each (rows of a run are <= 255 long)
-constexpr int kBlkMax = 64;  // descriptors a tile may have (the plan stores them at a stride of 16, 32 or 64)
+constexpr int kBlkMax = 64;  // descriptors a tile may have (the plan stores them at a stride of 8, 16, 32 or 64)
 constexpr int kBlkRows = 8;
 // (kBlkRunRows, mspmv_internal.h: rows per run)
 // (kBlkTileChunks, mspmv_internal.h: the chunks of a tile the LDS-staged and column-owner paths of
@@ -392,6 +393,33 @@ __global__ void k_build_blocks(const int *__restrict__ row_offsets, const int *_
         return;
     d0.y |= (unsigned)nd << 8;
     out[0] = d0;
+}
+
+// Pattern-column slots (TilePlan::d_pcols), one wave per descriptor slot of the repacked plan: chunk
+// di of tile t copies its wc offsets cols16[n0 + vofs + pstart + j0 ..] into its 128-B slot and repeats
+// the last one up to 64.  Slots without a chunk (and chunks of no column) keep the caller's zeros.
+__global__ __launch_bounds__(kBlock) void k_fill_pcols(const uint4 *__restrict__ blk, int stride,
+                                                       const int2 *__restrict__ bounds,
+                                                       const unsigned short *__restrict__ cols16, int num_tiles,
+                                                       unsigned short *__restrict__ pcols)
+{
+    const long long slot = (long long)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const int t = (int)(slot / stride), di = (int)(slot % stride);
+    if (t >= num_tiles)
+        return;
+    const int nd = (int)((blk[(size_t)t * stride].y >> 8) & 255u);
+    if (di >= nd)
+        return;
+    const uint4 d = blk[(size_t)t * stride + di];
+    const int vofs = d.x & 0xffff, j0 = (d.x >> 16) & 255, wc = d.x >> 24;
+    const int h = d.y & 15, p = (d.y >> 4) & 7;
+    if (wc == 0)
+        return;
+    int pstart = 0;
+    for (int i = 0; i < p && i < h; ++i)
+        pstart += blk_len(d, i);
+    pcols[(size_t)slot * 64 + lane] = cols16[(size_t)bounds[t].y + vofs + pstart + j0 + min(lane, wc - 1)];
 }
 
 // Per-tile choice of the in-tile reduction (one thread per tile, at plan time; gl = lanes per
@@ -489,6 +517,8 @@ struct TileArgs {
     const uint4 *blk;
     int blk_stride;
     int all_reg;
+    // ... the chunks' pattern columns, one 128-B slot per descriptor slot (TilePlan::d_pcols)
+    const unsigned short *pcols;
     // single-RHS plans with column dictionaries (TilePlan::d_dict; null: off)
     const int *dict;
     const int *ndict;
@@ -744,8 +774,15 @@ __device__ __forceinline__ uint4 blk_read(const uint4 &bd, int di)
                       (unsigned)__builtin_amdgcn_readlane((int)bd.w, di));
 }
 
+// Chunk di of tile t: its slot of pattern columns (TileArgs::pcols; position l is pattern column
+// j0 + l).  The address needs neither the tile's bounds nor the descriptor.
+__device__ __forceinline__ const unsigned short *blk_slot(const TileArgs &a, int t, int di)
+{
+    return a.pcols + ((size_t)t * a.blk_stride + di) * 64;
+}
+
 template <bool CG, bool NT, int TB, typename Head>
-__device__ __forceinline__ void blk_stage(const TileArgs &a, const uint4 &bd, int nd, int n0, int colbase,
+__device__ __forceinline__ void blk_stage(const TileArgs &a, int t, const uint4 &bd, int nd, int n0, int colbase,
                                           double *s_prod, double &beta, Head &&head)
 {
     constexpr int NW = TB / 64;  // waves sharing the tile
@@ -763,19 +800,18 @@ __device__ __forceinline__ void blk_stage(const TileArgs &a, const uint4 &bd, in
             if (di < nd) {  // wave-uniform
                 const uint4 d = blk_read(bd, di);
                 const int vofs = d.x & 0xffff, j0 = (d.x >> 16) & 255, wc = d.x >> 24;
-                const int h = d.y & 15, p = (d.y >> 4) & 7;
+                const int h = d.y & 15;
                 const int j = j0 + lane;
-                int start = 0, pstart = 0;
+                int start = 0;
 #pragma unroll
                 for (int i = 0; i < kBlkRows; ++i) {
-                    pstart = i == p ? start : pstart;
                     const int len = blk_len(d, i);
                     if (i < h && j < len)
                         st.v[s][i] = ld_stream<NT>(a.vals + n0 + vofs + start + j);
                     start += i < h ? len : 0;
                 }
                 if (lane < wc)
-                    st.c[s] = colbase + (int)ld_stream<NT>(a.cols16 + n0 + vofs + pstart + j);
+                    st.c[s] = colbase + (int)ld_stream<NT>(blk_slot(a, t, di) + lane);
             }
         }
 #pragma unroll
@@ -856,6 +892,17 @@ __device__ __forceinline__ double rows8_sum32(const double (&p)[kBlkRows])
     return v;
 }
 
+// The lane's two pattern columns of run slot di: ONE 4-B load of both 16-bit offsets from the slot's
+// line.  Unconditional: every slot of a tile exists (di < blk_stride, a multiple of the 8 run slots of
+// a round), and its address takes only t and the lane, so the load goes out beside the tile's header.
+template <bool NT>
+__device__ __forceinline__ unsigned blk_pair_cols(const TileArgs &a, int t, int round)
+{
+    const int lane = threadIdx.x & 63;
+    const int di = (int)(threadIdx.x >> 6) + (kBlock / 64) * (2 * round + (lane >> 5));
+    return ld_stream<NT>(reinterpret_cast<const unsigned *>(blk_slot(a, t, di)) + (lane & 31));
+}
+
 // Plain SpMV form of blk_rows with column PAIRS: each half-wave owns one run per round and its lane
 // l owns pattern columns 2l and 2l + 1, so a row of the run arrives in ONE 16-B load per lane (half
 // the value-load instructions of column-owner lanes; the loads may be 8-B aligned only -- gfx9's
@@ -865,27 +912,28 @@ __device__ __forceinline__ double rows8_sum32(const double (&p)[kBlkRows])
 // 24.98 vs 22.6-23.1 us (r03t).  Per chunk (descriptor bit 7): pattern columns in consecutive pairs
 // take ONE 16-B x load per lane.
 template <bool NT, int KR>
-__device__ __forceinline__ void blk_rows_pair(const TileArgs &a, const uint4 &bd, int nd, int r0, int n0,
-                                              int colbase)
+__device__ __forceinline__ void blk_rows_pair(const TileArgs &a, int t, unsigned cc, const uint4 &bd, int nd,
+                                              int r0, int n0, int colbase)
 {
     constexpr int NW = kBlock / 64;
     const int lane = threadIdx.x & 63;
     const int half = lane >> 5, hl = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     for (int round = 0; round * 2 * NW < nd; ++round) {
+        if (round > 0)  // round 0's came with the header (cc)
+            cc = blk_pair_cols<NT>(a, t, round);
         const int di = wave + NW * (2 * round + half);
         const bool valid = di < nd;
         const int src = min(di, nd - 1);  // descriptor lane (every wave holds all of them in bd)
         const uint4 d = make_uint4((unsigned)__shfl((int)bd.x, src), (unsigned)__shfl((int)bd.y, src),
                                    (unsigned)__shfl((int)bd.z, src), (unsigned)__shfl((int)bd.w, src));
         const int vofs = d.x & 0xffff, wc = d.x >> 24;
-        const int h = d.y & 15, p = (d.y >> 4) & 7, rofs = d.y >> 16;
+        const int h = d.y & 15, rofs = d.y >> 16;
         double2 v[KR];
         bool in0[KR], in1[KR];
-        int start = 0, pstart = 0;
+        int start = 0;
 #pragma unroll
         for (int i = 0; i < KR; ++i) {
-            pstart = i == p ? start : pstart;
             const int len = blk_len(d, i);
             in0[i] = valid && i < h && 2 * hl < len;
             in1[i] = valid && i < h && 2 * hl + 1 < len;
@@ -894,15 +942,12 @@ __device__ __forceinline__ void blk_rows_pair(const TileArgs &a, const uint4 &bd
                 v[i] = ld_stream<NT>(reinterpret_cast<const double2 *>(a.vals + n0 + vofs + start + 2 * hl));
             start += i < h ? len : 0;
         }
-        // the lane's two pattern columns: ONE 4-B load of both 16-bit offsets (2-B aligned at worst; the
-        // second belongs to the next position, in bounds by the stream's padding, and is replaced when
-        // the lane has one column), then ONE 16-B x load (8-B aligned at worst) for an adjacent pair --
+        // the lane's two pattern columns (cc, blk_pair_cols: positions past the chunk repeat its last
+        // column, a slot without a chunk holds the tile's column base; the second is replaced when the
+        // lane has one column), then ONE 16-B x load (8-B aligned at worst) for an adjacent pair --
         // FEM nodes list their unknowns consecutively, so nearly every lane's pair is -- and a second
         // load only in lanes whose pair is not (an exec-masked load, skipped when no lane needs it).
         // The load starts at n - 2 at most and picks its half (the last column sits at n - 1 at most).
-        unsigned cc = 0u;
-        if (valid && 2 * hl < wc)
-            cc = ld_stream<NT>(reinterpret_cast<const unsigned *>(a.cols16 + n0 + vofs + pstart + 2 * hl));
         const int c0 = colbase + (int)(cc & 0xffffu);
         const int c1 = (valid && 2 * hl + 1 < wc) ? colbase + (int)(cc >> 16) : c0 + 1;
         const int base = min(c0, a.n - 2);
@@ -930,8 +975,8 @@ __device__ __forceinline__ void blk_rows_pair(const TileArgs &a, const uint4 &bd
 // are reproducible and within 2 (len+1) eps (|A||x|)_i of the sequential CSR-order sum
 // (mspmv_tile_modes reports these tiles as 255).
 template <int MODE, bool NT, int TB, typename Head>
-__device__ __forceinline__ void blk_rows(const TileArgs &a, const uint4 &bd, int nd, int r0, int n0, int colbase,
-                                         double &beta, double &dot, Head &&head)
+__device__ __forceinline__ void blk_rows(const TileArgs &a, int t, const uint4 &bd, int nd, int r0, int n0,
+                                         int colbase, double &beta, double &dot, Head &&head)
 {
     constexpr bool CG = MODE == kModeCg;
     constexpr int NW = TB / 64;
@@ -952,18 +997,17 @@ __device__ __forceinline__ void blk_rows(const TileArgs &a, const uint4 &bd, int
             if (di < nd) {  // wave-uniform
                 const uint4 d = blk_read(bd, di);
                 const int vofs = d.x & 0xffff, wc = d.x >> 24;
-                const int h = d.y & 15, p = (d.y >> 4) & 7, rofs = d.y >> 16;
-                int start = 0, pstart = 0;
+                const int h = d.y & 15, rofs = d.y >> 16;
+                int start = 0;
 #pragma unroll
                 for (int i = 0; i < kBlkRows; ++i) {
-                    pstart = i == p ? start : pstart;
                     const int len = blk_len(d, i);
                     if (i < h && lane < len)
                         st.v[s][i] = ld_stream<NT>(a.vals + n0 + vofs + start + lane);
                     start += i < h ? len : 0;
                 }
                 if (lane < wc)
-                    st.c[s] = colbase + (int)ld_stream<NT>(a.cols16 + n0 + vofs + pstart + lane);
+                    st.c[s] = colbase + (int)ld_stream<NT>(blk_slot(a, t, di) + lane);
                 if (MODE != kModeSpmv && (lane & 7) == 0 && myrow < h) {
                     const int R = r0 + rofs + myrow;
                     if constexpr (CG)
@@ -1395,7 +1439,7 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(STAMP ? 8 : 
     const bool blk_reg = BLK && nblk > 0 && __ballot((tid & 63) < nblk && ((bd.x >> 16) & 255u) != 0) == 0;
     if constexpr (BLK) if (blk_reg) {
         double dot = 0.0;
-        blk_rows<MODE, NT, TB>(a, bd, nblk, r0, n0, colbase, beta, dot, [&]() {
+        blk_rows<MODE, NT, TB>(a, t, bd, nblk, r0, n0, colbase, beta, dot, [&]() {
             head();
             return go;
         });
@@ -1410,7 +1454,7 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(STAMP ? 8 : 
         return;
     }
     if (BLK && nblk > 0) {
-        blk_stage<CG, NT, TB>(a, bd, nblk, n0, colbase, sm.prod, beta, [&]() {
+        blk_stage<CG, NT, TB>(a, t, bd, nblk, n0, colbase, sm.prod, beta, [&]() {
             head();
             return go;
         });
@@ -1574,6 +1618,12 @@ __global__ __launch_bounds__(kBlock) void k_spmv_blk(TileArgs a)
     if constexpr (CG)
         part_load(a.part_in, a.n_part_in, pin);
     if constexpr (MODE == kModeSpmv && KR <= 6) {  // taller runs: 73 VGPRs, column owners
+        // round 0's pattern columns, issued with the header: the tile's chain is header -> x, as long
+        // as the values' header -> rows (a tile without runs reads its zeroed slot and drops it)
+        const unsigned cc = blk_pair_cols<NT>(a, t, 0);
+        // ... all of it consumed here, ahead of the exits below: left alone, the compiler sinks the
+        // bounds and the columns behind the descriptor count's test, one round trip each
+        asm volatile("" ::"s"(b0.x), "s"(b0.y), "s"(colbase), "v"(cc));
         if (stopped)
             return;
         // a register run tile: every chunk starts at pattern column 0 (wave-uniform: each wave holds
@@ -1588,10 +1638,10 @@ __global__ __launch_bounds__(kBlock) void k_spmv_blk(TileArgs a)
                 return;
             }
         }
-        blk_rows_pair<NT, KR>(a, bd, nblk, b0.x, b0.y, colbase);
+        blk_rows_pair<NT, KR>(a, t, cc, bd, nblk, b0.x, b0.y, colbase);
         return;
     }
-    blk_rows<MODE, NT, kBlock>(a, bd, nblk, b0.x, b0.y, colbase, beta, dot, [&]() {
+    blk_rows<MODE, NT, kBlock>(a, t, bd, nblk, b0.x, b0.y, colbase, beta, dot, [&]() {
         if (stopped)
             go = false;
         else if constexpr (CG)
@@ -2085,16 +2135,15 @@ k_spmm_blk(TileArgs a)
     auto fetch = [&](int di, int &cj, double (&vr)[KR]) {
         const uint4 d = blk_read(bd, di);
         const int vofs = d.x & 0xffff, wc = d.x >> 24;
-        const int h = d.y & 15, p = (d.y >> 4) & 7;
+        const int h = d.y & 15;
         int start[KR];
-        int pstart = 0, acc_s = 0;
+        int acc_s = 0;
 #pragma unroll
         for (int i = 0; i < KR; ++i) {
             start[i] = acc_s;
-            pstart = i == p ? acc_s : pstart;
             acc_s += i < h ? blk_len(d, i) : 0;
         }
-        cj = lane < wc ? colbase + (int)ld_stream<NT>(a.cols16 + n0 + vofs + pstart + lane) : 0;
+        cj = lane < wc ? colbase + (int)ld_stream<NT>(blk_slot(a, t, di) + lane) : 0;
 #pragma unroll
         for (int i = 0; i < KR; ++i)
             vr[i] = (i < h && lane < blk_len(d, i)) ? ld_stream<NT>(a.vals + n0 + vofs + start[i] + lane) : 0.0;
@@ -2458,6 +2507,17 @@ hipError_t launch_build_blocks(const int *d_row_offsets, const int *d_cols, cons
     return hipGetLastError();
 }
 
+hipError_t launch_fill_pcols(const uint4 *d_blk, int blk_stride, const int2 *d_bounds,
+                             const unsigned short *d_cols16, int num_tiles, unsigned short *d_pcols, hipStream_t s)
+{
+    if (num_tiles <= 0)
+        return hipSuccess;
+    const long long slots = (long long)num_tiles * blk_stride;  // blk_stride is a multiple of kBlock / 64
+    hipLaunchKernelGGL(k_fill_pcols, dim3((unsigned)(slots / (kBlock / 64))), dim3(kBlock), 0, s, d_blk, blk_stride,
+                       d_bounds, d_cols16, num_tiles, d_pcols);
+    return hipGetLastError();
+}
+
 // multi: an L-wide plan (dictionaries of at most spmm_dict_max(L) entries: what its kernel parks in
 // LDS; the kernel checks the limit again)
 hipError_t launch_build_dict(const int *d_cols, const int2 *d_bounds, int num_tiles, int max_items, int *d_dict,
@@ -2523,6 +2583,7 @@ static TileArgs make_args(mspmv_handle_s *h, const TilePlan &plan, const double 
         a.cols16 = plan.d_cols16;
         a.blk = plan.d_blk;
         a.blk_stride = plan.blk_stride;
+        a.pcols = plan.d_pcols;
         // L > 1 runs the node-block plan only while k_spmm_blk is enabled (get_plan's gate): L = 2
         // shares the single-RHS tile size, so without this the switched-off plan would still be all-reg
         a.all_reg = plan.d_blk && plan.num_tiles_reg == plan.num_tiles && (L == 1 || spmm_blk_enabled());

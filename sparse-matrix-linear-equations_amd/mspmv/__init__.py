@@ -133,6 +133,7 @@ _SIGS = {
     "mspmv_tile_streams": (_I, [_P, _PI, _PI]),
     "mspmv_plan_dict_tiles": (_I, [_P, _I, _PI]),
     "mspmv_plan_block_tiles": (_I, [_P, _I, _PI]),
+    "mspmv_plan_block_rounds": (_I, [_P, _I, _PI]),
     "mspmv_tile_modes": (_I, [_P, _I, _P]),
     "mspmv_tile_lanes": (_I, [_P, _I, _PI]),
     "mspmv_offset_windows": (_I, [ctypes.POINTER(_CsrD), _D, _D, _PI, _PI, ctypes.POINTER(ctypes.c_longlong), _PI, _P,
@@ -571,6 +572,12 @@ class GpuCsr:
         """Tiles of the L-column plan staged by node blocks (mspmv_plan_block_tiles)."""
         n = ctypes.c_int()
         _check(lib.mspmv_plan_block_tiles(self.h, L, ctypes.byref(n)), "plan_block_tiles")
+        return n.value
+
+    def plan_block_rounds(self, L: int = 1) -> int:
+        """Node-block tiles of more than one round of run slots, > 8 chunks (mspmv_plan_block_rounds)."""
+        n = ctypes.c_int()
+        _check(lib.mspmv_plan_block_rounds(self.h, L, ctypes.byref(n)), "plan_block_rounds")
         return n.value
 
     def spmv(self, x: np.ndarray) -> np.ndarray:
