@@ -421,6 +421,20 @@ MSPMV_API mspmv_status mspmv_plan_block_tiles(mspmv_handle h, int L, int *tiles_
 /* Of those, the tiles with more than 8 run chunks (*tiles_two_rounds): the column-pair kernel takes
  * them in a second round of its eight half-wave run slots. */
 MSPMV_API mspmv_status mspmv_plan_block_rounds(mspmv_handle h, int L, int *tiles_two_rounds);
+/* The run chunks of the plan's register run tiles by how the column-pair SpMV reads their pattern
+ * columns: from the chunk's 64-B record, as at most 12 runs of consecutive columns (*chunks_compact),
+ * or, a pattern of more such runs, from its row of the 16-bit column stream (*chunks_escaped).  Both 0
+ * for plans without node blocks. */
+MSPMV_API mspmv_status mspmv_plan_block_records(mspmv_handle h, int L, int *chunks_compact, int *chunks_escaped);
+/* Host-only test hooks on the record's codec, no device needed.  Encode: a pattern of wc (0..64)
+ * sorted distinct 16-bit column offsets into entries[12] (start | len << 16 | prefix << 24 per run of
+ * consecutive columns, unused entries 0); *escaped = 1 and no entry when there are more than 12 runs.
+ * Decode: the offset at pattern position q (>= 0) of a whole record (16 dwords: the descriptor, whose
+ * dword 0 holds wc in bits 24-31, then the 12 entries); positions >= wc give that of wc - 1, an
+ * all-zero record 0. */
+MSPMV_API mspmv_status mspmv_block_record_encode(const unsigned short *offsets, int wc, unsigned *entries,
+                                                 int *escaped);
+MSPMV_API mspmv_status mspmv_block_record_decode(const unsigned *record, int q, unsigned *offset);
 /* Each tile's in-tile reduction for L right-hand sides (num_tiles entries; 255 = a node-block
  * tile summed in registers by a fixed lane tree, see mspmv_plan_block_tiles): 0 = merge walk
  * (one walker per thread, or per L/2 lanes), g > 0 = row groups with 2^(g-1) nonzero-parallel

@@ -102,6 +102,7 @@ static void free_plan(TilePlan &p)
     dev_free(p.d_idx16);
     dev_free(p.d_blk);
     dev_free(p.d_pcols);
+    dev_free(p.d_recs);
     free_slab(p.slab);
     p.slab = nullptr;
     free_dia(p.dia);
@@ -526,6 +527,30 @@ static mspmv_status build_plan(mspmv_handle_s *h, int L, const TilePlan **out, i
                 set_error(std::string("node blocks: pattern-column slots: ") + hipGetErrorString(e));
                 return fail(MSPMV_ERR_HIP);
             }
+            // descriptor and pattern once more as one 64-B record per descriptor slot, which is all the
+            // column-pair SpMV reads of a run (blk_rec_encode)
+            int *d_counts = nullptr;
+            int counts[2] = {0, 0};
+            if ((st = dev_alloc(&p.d_recs, packed.size() * kRecDwords)) != MSPMV_OK)
+                return fail(st);
+            if ((st = dev_alloc(&d_counts, (size_t)2)) != MSPMV_OK)
+                return fail(st);
+            e = hipMemsetAsync(p.d_recs, 0, sizeof(unsigned) * packed.size() * kRecDwords, h->stream);
+            if (e == hipSuccess)
+                e = hipMemsetAsync(d_counts, 0, sizeof(counts), h->stream);
+            if (e == hipSuccess)
+                e = launch_fill_recs(p.d_blk, p.blk_stride, p.d_pcols, T, p.d_recs, d_counts, h->stream);
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(counts, d_counts, sizeof(counts), hipMemcpyDeviceToHost, h->stream);
+            if (e == hipSuccess)
+                e = hipStreamSynchronize(h->stream);
+            dev_free(d_counts);
+            if (e != hipSuccess) {
+                set_error(std::string("node blocks: records: ") + hipGetErrorString(e));
+                return fail(MSPMV_ERR_HIP);
+            }
+            p.blk_rec_compact = counts[0];
+            p.blk_rec_escaped = counts[1];
         }
     }
     // multi-RHS: only the L = 16 plan (k_spmm_tile's DICT path runs at L = 16 only); not the run-
@@ -3138,6 +3163,40 @@ mspmv_status mspmv_plan_block_rounds(mspmv_handle h, int L, int *tiles_two_round
     const TilePlan *plan = nullptr;
     ST_TRY(get_plan(h, L, &plan, true));
     *tiles_two_rounds = plan->d_blk ? plan->blk_two_rounds : 0;
+    return MSPMV_OK;
+}
+
+mspmv_status mspmv_plan_block_records(mspmv_handle h, int L, int *chunks_compact, int *chunks_escaped)
+{
+    ST_TRY(check_handle(h));
+    if (!chunks_compact || !chunks_escaped)
+        return invalid("null out pointer");
+    if (!supported_L(L))
+        return (set_error("L must be one of 1, 2, 4, 8, 16"), MSPMV_ERR_UNSUPPORTED);
+    const TilePlan *plan = nullptr;
+    ST_TRY(get_plan(h, L, &plan, true));
+    *chunks_compact = plan->d_recs ? plan->blk_rec_compact : 0;
+    *chunks_escaped = plan->d_recs ? plan->blk_rec_escaped : 0;
+    return MSPMV_OK;
+}
+
+mspmv_status mspmv_block_record_encode(const unsigned short *offsets, int wc, unsigned *entries, int *escaped)
+{
+    if (!entries || !escaped || (wc > 0 && !offsets))
+        return invalid("null pointer");
+    if (wc < 0 || wc > 64)
+        return invalid("a chunk holds 0..64 pattern columns");
+    *escaped = blk_rec_encode(offsets, wc, entries) ? 0 : 1;
+    return MSPMV_OK;
+}
+
+mspmv_status mspmv_block_record_decode(const unsigned *record, int q, unsigned *offset)
+{
+    if (!record || !offset)
+        return invalid("null pointer");
+    if (q < 0)
+        return invalid("q >= 0");
+    *offset = blk_rec_decode(record + 4, (int)(record[0] >> 24), q);
     return MSPMV_OK;
 }
 

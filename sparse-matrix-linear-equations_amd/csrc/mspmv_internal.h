@@ -186,7 +186,12 @@ struct TilePlan {
     // colbase[t]), positions wc .. 63 repeating the last one; slots without a chunk are zero, so every
     // position names a column of the tile's range.  A slot's address needs no descriptor.
     unsigned short *d_pcols = nullptr;  // [num_tiles * blk_stride * 64]
-    int num_tiles_blk = 0;              // tiles staged by node blocks
+    // ... and, for the column-pair SpMV alone, descriptor and pattern once more as one 64-B record per
+    // descriptor slot (blk_rec_*, below; k_fill_recs): what a half-wave reads of its run in one load.
+    unsigned *d_recs = nullptr;         // [num_tiles * blk_stride * kRecDwords]
+    int blk_rec_compact = 0;            // chunks of register run tiles whose pattern the record holds
+    int blk_rec_escaped = 0;            // ... and those of more than kRecEntries column-runs (read in cols16)
+    int num_tiles_blk = 0;             // tiles staged by node blocks
     int num_tiles_reg = 0;              // of those, tiles reduced in registers (h_blk_reg)
     int blk_rows_max = 8;               // the tallest run (rows of one node) over the descriptors
     bool blk_spmv = false;              // the plain SpMV runs k_spmv_blk (most tiles register run tiles;
@@ -487,6 +492,87 @@ hipError_t launch_build_blocks(const int *d_row_offsets, const int *d_cols, cons
 // TilePlan::d_pcols (zeroed by the caller) from the repacked descriptors and cols16.
 hipError_t launch_fill_pcols(const uint4 *d_blk, int blk_stride, const int2 *d_bounds,
                              const unsigned short *d_cols16, int num_tiles, unsigned short *d_pcols, hipStream_t s);
+// Node-block records (TilePlan::d_recs): 16 dwords per descriptor slot of a register run tile.
+//   dwords 0-3:  the chunk's descriptor (j0 is 0 in such tiles), with the TILE's descriptor count in
+//                y bits 8-15 of EVERY record of the tile, a slot without a chunk included (h = 0
+//                marks it; its other dwords are zero), so a wave needs its own two records only;
+//                y bit 7 (spare in the descriptor): kRecEscape.  Tiles the column-pair kernel does
+//                not reduce in registers have all-zero records (count 0: its register fallback).
+//   dwords 4-15: the pattern's column-runs (maximal stretches of consecutive columns), in order:
+//                start (the 16-bit offset of cols16, bits 0-15) | len (1..64, 16-23) | prefix (the
+//                pattern position of the run's first column, 24-31); unused entries are zero.
+// Position q of the pattern is start[e] + q - prefix[e] for the last entry e with prefix[e] <= q;
+// positions past the chunk decode as its last column and an all-zero record as offset 0, so every
+// position names a column of the tile's range.  A pattern of more than kRecEntries column-runs sets
+// kRecEscape and keeps no entry: its readers take the pattern row in cols16.
+// Record (t, di) sits at slot blk_rec_pos(di) of tile t: within each round of eight run slots the
+// two a wave reads (di = wave and wave + 4) are the two halves of one 128-B line.
+constexpr int kRecDwords = 16;
+constexpr int kRecEntries = 12;
+constexpr unsigned kRecEscape = 1u << 7;
+
+__host__ __device__ inline int blk_rec_pos(int di)
+{
+    return (di & ~7) | ((di & 3) << 1) | ((di >> 2) & 1);
+}
+
+// The column-runs of pattern P (wc sorted distinct offsets) into ent[kRecEntries]; false (and no
+// entry) when there are more.
+__host__ __device__ inline bool blk_rec_encode(const unsigned short *P, int wc, unsigned *ent)
+{
+    for (int e = 0; e < kRecEntries; ++e)
+        ent[e] = 0u;
+    int ne = 0;
+    for (int q = 0; q < wc;) {
+        int len = 1;
+        while (q + len < wc && (int)P[q + len] == (int)P[q] + len)
+            ++len;
+        if (ne == kRecEntries) {
+            for (int e = 0; e < kRecEntries; ++e)
+                ent[e] = 0u;
+            return false;
+        }
+        ent[ne++] = (unsigned)P[q] | ((unsigned)len << 16) | ((unsigned)q << 24);
+        q += len;
+    }
+    return true;
+}
+
+// The entry holding position q (q < wc, or 0): a branch-free binary search, four probes of the
+// twelve entries through ent(e) -- an array on the host, a cross-lane read in the kernel.  e is
+// its index.  (E - 1) >> 24 is E's prefix, and 255 for an unused entry: those sort last.
+template <typename F>
+__host__ __device__ inline unsigned blk_rec_find(F &&ent, int q, int &e)
+{
+    e = 0;
+    unsigned E = ent(0);
+#pragma unroll
+    for (int step = 8; step > 0; step >>= 1) {
+        const int c = e + step;  // 12 at most (8 + 4), past the entries
+        const bool in = c < kRecEntries;
+        const unsigned Ec = ent(in ? c : e);
+        if (in && (int)((Ec - 1u) >> 24) <= q) {
+            e = c;
+            E = Ec;
+        }
+    }
+    return E;
+}
+
+// Position q of a record's pattern, as a 16-bit column offset.
+__host__ __device__ inline unsigned blk_rec_decode(const unsigned *ent, int wc, int q)
+{
+    q = q < wc ? q : wc - 1;
+    q = q < 0 ? 0 : q;
+    int e;
+    const unsigned E = blk_rec_find([&](int i) { return ent[i]; }, q, e);
+    return (E & 0xffffu) + (unsigned)q - (E >> 24);
+}
+
+// TilePlan::d_recs (zeroed by the caller) from the repacked descriptors and their pattern-column
+// slots; counts[0] / counts[1] (zeroed too) take the chunks encoded / escaped.
+hipError_t launch_fill_recs(const uint4 *d_blk, int blk_stride, const unsigned short *d_pcols, int num_tiles,
+                            unsigned *d_recs, int *d_counts, hipStream_t s);
 hipError_t launch_build_dict(const int *d_cols, const int2 *d_bounds, int num_tiles, int max_items, int *d_dict,
                              int *d_ndict, unsigned short *d_idx16, hipStream_t s, bool multi, int L = 1);
 // Multi-RHS column dictionaries: the distinct panel rows a tile parks in LDS, 8 KB per workgroup

@@ -422,6 +422,42 @@ __global__ __launch_bounds__(kBlock) void k_fill_pcols(const uint4 *__restrict__
     pcols[(size_t)slot * 64 + lane] = cols16[(size_t)bounds[t].y + vofs + pstart + j0 + min(lane, wc - 1)];
 }
 
+// Node-block records (TilePlan::d_recs, layout at blk_rec_encode), one thread per descriptor slot of
+// the repacked plan, after k_fill_pcols: a register run tile's chunk di puts its descriptor and the
+// column-runs of its slot's pattern into record blk_rec_pos(di); its slots without a chunk take the
+// tile's count alone.  Other tiles keep the caller's zeros.
+__global__ __launch_bounds__(kBlock) void k_fill_recs(const uint4 *__restrict__ blk, int stride,
+                                                      const unsigned short *__restrict__ pcols, int num_tiles,
+                                                      unsigned *__restrict__ recs, int *__restrict__ counts)
+{
+    const long long slot = (long long)blockIdx.x * kBlock + threadIdx.x;
+    const int t = (int)(slot / stride), di = (int)(slot % stride);
+    if (t >= num_tiles)
+        return;
+    const uint4 *tb = blk + (size_t)t * stride;
+    const int nd = (int)((tb[0].y >> 8) & 255u);
+    bool reg = nd > 0;  // the kernel's former test: every chunk starts at pattern column 0
+    for (int i = 0; i < nd; ++i)
+        reg = reg && ((tb[i].x >> 16) & 255u) == 0;
+    if (!reg)
+        return;
+    unsigned *out = recs + ((size_t)t * stride + blk_rec_pos(di)) * kRecDwords;
+    if (di >= nd) {
+        out[1] = (unsigned)nd << 8;
+        return;
+    }
+    const uint4 d = tb[di];
+    unsigned ent[kRecEntries];
+    const bool fits = blk_rec_encode(pcols + (size_t)slot * 64, (int)(d.x >> 24), ent);
+    atomicAdd(&counts[fits ? 0 : 1], 1);
+    out[0] = d.x;
+    out[1] = (d.y & ~0xff80u) | ((unsigned)nd << 8) | (fits ? 0u : kRecEscape);
+    out[2] = d.z;
+    out[3] = d.w;
+    for (int e = 0; e < kRecEntries; ++e)
+        out[4 + e] = ent[e];
+}
+
 // Per-tile choice of the in-tile reduction (one thread per tile, at plan time; gl = lanes per
 // nonzero: 1 for SpMV, L/2 column-pair lanes for SpMM).  The tile's row segments -- its complete rows plus the trailing partial row of a
 // split boundary -- are either summed by row groups of G = 2^lg lanes (mode lg + 1) or, when
@@ -519,6 +555,8 @@ struct TileArgs {
     int all_reg;
     // ... the chunks' pattern columns, one 128-B slot per descriptor slot (TilePlan::d_pcols)
     const unsigned short *pcols;
+    // ... descriptor and pattern as one 64-B record per descriptor slot (TilePlan::d_recs)
+    const unsigned *recs;
     // single-RHS plans with column dictionaries (TilePlan::d_dict; null: off)
     const int *dict;
     const int *ndict;
@@ -892,15 +930,17 @@ __device__ __forceinline__ double rows8_sum32(const double (&p)[kBlkRows])
     return v;
 }
 
-// The lane's two pattern columns of run slot di: ONE 4-B load of both 16-bit offsets from the slot's
-// line.  Unconditional: every slot of a tile exists (di < blk_stride, a multiple of the 8 run slots of
-// a round), and its address takes only t and the lane, so the load goes out beside the tile's header.
+// The half-wave's record of a round (TilePlan::d_recs): lane l of each half loads dword l & 15 of the
+// record of the half's run slot, ONE 4-B load and one 64-B half line per half, the two halves of a
+// wave sharing a line (blk_rec_pos).  Unconditional: every slot of a tile exists (di < blk_stride, a
+// multiple of the 8 run slots of a round), and its address takes only t and the lane, so the load
+// goes out with the tile's header and IS its descriptor.
 template <bool NT>
-__device__ __forceinline__ unsigned blk_pair_cols(const TileArgs &a, int t, int round)
+__device__ __forceinline__ unsigned blk_pair_rec(const TileArgs &a, int t, int round)
 {
     const int lane = threadIdx.x & 63;
-    const int di = (int)(threadIdx.x >> 6) + (kBlock / 64) * (2 * round + (lane >> 5));
-    return ld_stream<NT>(reinterpret_cast<const unsigned *>(blk_slot(a, t, di)) + (lane & 31));
+    const int slot = 8 * round + 2 * (int)(threadIdx.x >> 6) + (lane >> 5);  // blk_rec_pos(wave + 4 (2 round + half))
+    return ld_stream<NT>(a.recs + ((size_t)t * a.blk_stride + slot) * kRecDwords + (lane & 15));
 }
 
 // Plain SpMV form of blk_rows with column PAIRS: each half-wave owns one run per round and its lane
@@ -909,24 +949,24 @@ __device__ __forceinline__ unsigned blk_pair_cols(const TileArgs &a, int t, int 
 // unaligned access mode), and one rows8_sum32 folds both halves' runs (half the shuffles).  A
 // lane's two products are added before the half-wave tree: a fixed order, so rows stay
 // reproducible and within the reordering bound (mode 255).  Column-owner lanes instead: pwtk shape
-// 24.98 vs 22.6-23.1 us (r03t).  Per chunk (descriptor bit 7): pattern columns in consecutive pairs
-// take ONE 16-B x load per lane.
+// 24.98 vs 22.6-23.1 us (r03t).  Pattern columns in consecutive pairs take ONE 16-B x load per lane.
+// Descriptor and pattern columns come from the half's record (rec, blk_pair_rec) by cross-lane
+// reads inside the half; nd is the tile's count, which every record carries.
 template <bool NT, int KR>
-__device__ __forceinline__ void blk_rows_pair(const TileArgs &a, int t, unsigned cc, const uint4 &bd, int nd,
-                                              int r0, int n0, int colbase)
+__device__ __forceinline__ void blk_rows_pair(const TileArgs &a, int t, unsigned rec, int nd, int r0, int n0,
+                                              int colbase)
 {
     constexpr int NW = kBlock / 64;
     const int lane = threadIdx.x & 63;
     const int half = lane >> 5, hl = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     for (int round = 0; round * 2 * NW < nd; ++round) {
-        if (round > 0)  // round 0's came with the header (cc)
-            cc = blk_pair_cols<NT>(a, t, round);
+        if (round > 0)  // round 0's came with the header
+            rec = blk_pair_rec<NT>(a, t, round);
         const int di = wave + NW * (2 * round + half);
-        const bool valid = di < nd;
-        const int src = min(di, nd - 1);  // descriptor lane (every wave holds all of them in bd)
-        const uint4 d = make_uint4((unsigned)__shfl((int)bd.x, src), (unsigned)__shfl((int)bd.y, src),
-                                   (unsigned)__shfl((int)bd.z, src), (unsigned)__shfl((int)bd.w, src));
+        const bool valid = di < nd;  // else the record holds the count alone: no row, no column-run
+        auto dword = [&](int k) { return (unsigned)__shfl((int)rec, (lane & 32) + k); };
+        const uint4 d = make_uint4(dword(0), dword(1), dword(2), dword(3));
         const int vofs = d.x & 0xffff, wc = d.x >> 24;
         const int h = d.y & 15, rofs = d.y >> 16;
         double2 v[KR];
@@ -942,14 +982,36 @@ __device__ __forceinline__ void blk_rows_pair(const TileArgs &a, int t, unsigned
                 v[i] = ld_stream<NT>(reinterpret_cast<const double2 *>(a.vals + n0 + vofs + start + 2 * hl));
             start += i < h ? len : 0;
         }
-        // the lane's two pattern columns (cc, blk_pair_cols: positions past the chunk repeat its last
-        // column, a slot without a chunk holds the tile's column base; the second is replaced when the
-        // lane has one column), then ONE 16-B x load (8-B aligned at worst) for an adjacent pair --
-        // FEM nodes list their unknowns consecutively, so nearly every lane's pair is -- and a second
-        // load only in lanes whose pair is not (an exec-masked load, skipped when no lane needs it).
+        // the lane's two pattern columns, positions 2 hl and 2 hl + 1 of the record's column-runs
+        // (positions past the chunk repeat its last column, a record without a chunk gives the tile's
+        // column base): the second is the first plus one unless it opens the next column-run.  Then
+        // ONE 16-B x load (8-B aligned at worst) for an adjacent pair -- FEM nodes list their
+        // unknowns consecutively, so nearly every lane's pair is -- and a second load only in lanes
+        // whose pair is not (an exec-masked load, skipped when no lane needs it).
         // The load starts at n - 2 at most and picks its half (the last column sits at n - 1 at most).
-        const int c0 = colbase + (int)(cc & 0xffffu);
-        const int c1 = (valid && 2 * hl + 1 < wc) ? colbase + (int)(cc >> 16) : c0 + 1;
+        const int q = max(min(2 * hl, wc - 1), 0);
+        int e;
+        const unsigned E = blk_rec_find([&](int i) { return dword(4 + i); }, q, e);
+        const unsigned En = dword(4 + min(e + 1, kRecEntries - 1));
+        int c0 = colbase + (int)((E & 0xffffu) + (unsigned)q - (E >> 24));
+        int c1 = c0 + 1;
+        if (2 * hl + 1 < wc && 2 * hl + 1 == (int)((E >> 24) + ((E >> 16) & 255u)))
+            c1 = colbase + (int)(En & 0xffffu);
+        if (d.y & kRecEscape) {
+            // more column-runs than a record holds: both 16-bit offsets in ONE 4-B load from the
+            // pattern row in cols16 (2-B aligned at worst; the second belongs to the next position,
+            // in bounds by the stream's padding, and is replaced when the lane has one column)
+            const int p = (d.y >> 4) & 7;
+            int pstart = 0;
+#pragma unroll
+            for (int i = 0; i < KR - 1; ++i)
+                pstart += i < p ? blk_len(d, i) : 0;
+            unsigned cc = 0u;
+            if (2 * hl < wc)
+                cc = ld_stream<NT>(reinterpret_cast<const unsigned *>(a.cols16 + n0 + vofs + pstart + 2 * hl));
+            c0 = colbase + (int)(cc & 0xffffu);
+            c1 = 2 * hl + 1 < wc ? colbase + (int)(cc >> 16) : c0 + 1;
+        }
         const int base = min(c0, a.n - 2);
         const double2 xx = *reinterpret_cast<const double2 *>(a.x + base);
         const double x0 = base == c0 ? xx.x : xx.y;
@@ -1596,7 +1658,7 @@ struct BlkSmem {
 };
 
 // FB (plain SpMV): the plan has tiles that are not register run tiles, so the register fallback is
-// compiled in; without it the kernel takes 62 SGPRs, with it 84 -- and 256-thread workgroups are
+// compiled in; without it the kernel takes 64 SGPRs, with it 88 -- and 256-thread workgroups are
 // admitted 8 per CU only up to .sgpr_count 80 (7 at 82-96, MI355X_MICROARCH.md "Residency"), so plans
 // of run tiles only keep the lean form.
 template <int MODE, bool NT, int KR = kBlkRows, bool FB = false>
@@ -1618,19 +1680,20 @@ __global__ __launch_bounds__(kBlock) void k_spmv_blk(TileArgs a)
     if constexpr (CG)
         part_load(a.part_in, a.n_part_in, pin);
     if constexpr (MODE == kModeSpmv && KR <= 6) {  // taller runs: 73 VGPRs, column owners
-        // round 0's pattern columns, issued with the header: the tile's chain is header -> x, as long
-        // as the values' header -> rows (a tile without runs reads its zeroed slot and drops it)
-        const unsigned cc = blk_pair_cols<NT>(a, t, 0);
+        // round 0's records, issued with the header: descriptor and pattern columns in one load, so the
+        // tile's chain is header -> x, as long as the values' header -> rows (a tile without runs reads
+        // its zeroed records and drops them)
+        const unsigned rec = blk_pair_rec<NT>(a, t, 0);
         // ... all of it consumed here, ahead of the exits below: left alone, the compiler sinks the
-        // bounds and the columns behind the descriptor count's test, one round trip each
-        asm volatile("" ::"s"(b0.x), "s"(b0.y), "s"(colbase), "v"(cc));
+        // bounds and the record behind the stop test, one round trip each
+        asm volatile("" ::"s"(b0.x), "s"(b0.y), "s"(colbase), "v"(rec));
         if (stopped)
             return;
-        // a register run tile: every chunk starts at pattern column 0 (wave-uniform: each wave holds
-        // all descriptors)
+        // the tile's descriptor count, in every record (lane 1: dword 1 of the first half's); 0 unless
+        // the tile is a register run tile (k_fill_recs)
+        const int nrec = (int)(((unsigned)__builtin_amdgcn_readlane((int)rec, 1) >> 8) & 255u);
         if constexpr (FB) {
-            const bool reg = nblk > 0 && __ballot((tid & 63) < nblk && ((bd.x >> 16) & 255u) != 0) == 0;
-            if (!reg) {
+            if (nrec == 0) {
                 const int4 fx = load_fix(a, t);
                 a.y0 = fx.z > 0 ? a.head_val + t : a.y + b0.x;
                 tile_rows_reg<NT>(a, t, b0.x, b0.y, a.cols16 ? colbase : -1);
@@ -1638,7 +1701,7 @@ __global__ __launch_bounds__(kBlock) void k_spmv_blk(TileArgs a)
                 return;
             }
         }
-        blk_rows_pair<NT, KR>(a, t, cc, bd, nblk, b0.x, b0.y, colbase);
+        blk_rows_pair<NT, KR>(a, t, rec, nrec, b0.x, b0.y, colbase);
         return;
     }
     blk_rows<MODE, NT, kBlock>(a, t, bd, nblk, b0.x, b0.y, colbase, beta, dot, [&]() {
@@ -2518,6 +2581,17 @@ hipError_t launch_fill_pcols(const uint4 *d_blk, int blk_stride, const int2 *d_b
     return hipGetLastError();
 }
 
+hipError_t launch_fill_recs(const uint4 *d_blk, int blk_stride, const unsigned short *d_pcols, int num_tiles,
+                            unsigned *d_recs, int *d_counts, hipStream_t s)
+{
+    if (num_tiles <= 0)
+        return hipSuccess;
+    const long long slots = (long long)num_tiles * blk_stride;
+    hipLaunchKernelGGL(k_fill_recs, dim3((unsigned)((slots + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, d_blk,
+                       blk_stride, d_pcols, num_tiles, d_recs, d_counts);
+    return hipGetLastError();
+}
+
 // multi: an L-wide plan (dictionaries of at most spmm_dict_max(L) entries: what its kernel parks in
 // LDS; the kernel checks the limit again)
 hipError_t launch_build_dict(const int *d_cols, const int2 *d_bounds, int num_tiles, int max_items, int *d_dict,
@@ -2584,6 +2658,7 @@ static TileArgs make_args(mspmv_handle_s *h, const TilePlan &plan, const double 
         a.blk = plan.d_blk;
         a.blk_stride = plan.blk_stride;
         a.pcols = plan.d_pcols;
+        a.recs = plan.d_recs;
         // L > 1 runs the node-block plan only while k_spmm_blk is enabled (get_plan's gate): L = 2
         // shares the single-RHS tile size, so without this the switched-off plan would still be all-reg
         a.all_reg = plan.d_blk && plan.num_tiles_reg == plan.num_tiles && (L == 1 || spmm_blk_enabled());

@@ -134,6 +134,9 @@ _SIGS = {
     "mspmv_plan_dict_tiles": (_I, [_P, _I, _PI]),
     "mspmv_plan_block_tiles": (_I, [_P, _I, _PI]),
     "mspmv_plan_block_rounds": (_I, [_P, _I, _PI]),
+    "mspmv_plan_block_records": (_I, [_P, _I, _PI, _PI]),
+    "mspmv_block_record_encode": (_I, [_P, _I, _P, _PI]),
+    "mspmv_block_record_decode": (_I, [_P, _I, ctypes.POINTER(ctypes.c_uint)]),
     "mspmv_tile_modes": (_I, [_P, _I, _P]),
     "mspmv_tile_lanes": (_I, [_P, _I, _PI]),
     "mspmv_offset_windows": (_I, [ctypes.POINTER(_CsrD), _D, _D, _PI, _PI, ctypes.POINTER(ctypes.c_longlong), _PI, _P,
@@ -580,6 +583,13 @@ class GpuCsr:
         _check(lib.mspmv_plan_block_rounds(self.h, L, ctypes.byref(n)), "plan_block_rounds")
         return n.value
 
+    def plan_block_records(self, L: int = 1):
+        """(chunks_compact, chunks_escaped): run chunks of register run tiles whose pattern columns the
+        column-pair SpMV reads from their 64-B record / from the column stream (mspmv_plan_block_records)."""
+        c, e = ctypes.c_int(), ctypes.c_int()
+        _check(lib.mspmv_plan_block_records(self.h, L, ctypes.byref(c), ctypes.byref(e)), "plan_block_records")
+        return c.value, e.value
+
     def spmv(self, x: np.ndarray) -> np.ndarray:
         x = np.ascontiguousarray(x, np.float64)
         assert x.shape == (self.num_cols,)
@@ -955,6 +965,26 @@ def offset_windows(a: CsrMatrix, min_fill: float = 0.85, min_window_fill: float 
         return None
     return {"windows": nw.value, "sum_offsets": sk.value, "masked_windows": mw.value, "k": k[: nw.value],
             "remainder": rem.value}
+
+
+def block_record_encode(offsets) -> tuple:
+    """(entries, escaped): a chunk's pattern (<= 64 sorted distinct 16-bit column offsets) as the <= 12
+    column-run entries of its node-block record (mspmv_block_record_encode; host only)."""
+    p = np.ascontiguousarray(offsets, np.uint16)
+    ent = np.zeros(12, np.uint32)
+    esc = ctypes.c_int()
+    _check(lib.mspmv_block_record_encode(_ptr(p), p.size, _ptr(ent), ctypes.byref(esc)), "block_record_encode")
+    return ent, bool(esc.value)
+
+
+def block_record_decode(record, q: int) -> int:
+    """The column offset at pattern position q of a 16-dword record: descriptor (wc in dword 0, bits
+    24-31), then the 12 entries (mspmv_block_record_decode; host only)."""
+    rec = np.ascontiguousarray(record, np.uint32)
+    assert rec.size == 16
+    out = ctypes.c_uint()
+    _check(lib.mspmv_block_record_decode(_ptr(rec), q, ctypes.byref(out)), "block_record_decode")
+    return out.value
 
 
 def spai_values(a: CsrMatrix) -> np.ndarray:

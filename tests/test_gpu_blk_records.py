@@ -1,0 +1,224 @@
+"""GPU: the column-pair node-block SpMV on 64-B records (TilePlan::d_recs).
+
+k_spmv_blk<0, NT, 6, FB> reads a run's descriptor and its pattern columns, run-length coded as at
+most 12 runs of consecutive columns, from one 64-B record per run slot; a pattern of more such runs
+escapes to its row of the 16-bit column stream.  Products, sums and their order are what they were, so
+on plans of register run tiles alone (kernel name ending ",6,false>") y is the pair tree of each row,
+restated in numpy here and required bit for bit: prod[k] = val[k] * x[col[k]] padded with +0.0 to 64,
+pair[l] = prod[2l] + prod[2l+1], then halves of 16, 8, 4, 2, 1.  Mixed plans are checked against the
+oracle under check_parity."""
+import numpy as np
+import pytest
+
+import mspmv
+from gpu_common import check_parity
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _need_gpu(gpu_available):
+    return gpu_available
+
+
+def pair_tree_spmv(a, x):
+    """y of the column-pair kernel for a matrix whose rows hold <= 64 entries, bit for bit."""
+    ro = a.row_offsets.astype(np.int64)
+    lens = np.diff(ro)
+    assert lens.max() <= 64
+    prod = np.zeros((a.num_rows, 64))
+    row = np.repeat(np.arange(a.num_rows), lens)
+    pos = np.arange(a.num_nonzeros) - ro[row]
+    prod[row, pos] = a.values * x[a.column_indices]
+    s = prod[:, 0::2] + prod[:, 1::2]
+    while s.shape[1] > 1:
+        w = s.shape[1] // 2
+        s = s[:, :w] + s[:, w:]
+    return s[:, 0]
+
+
+def count_chunks(a, bounds):
+    """Run chunks of a plan of whole-row tiles, as the plan forms them: within a tile, up to 6 consecutive
+    rows whose column lists are prefixes of one list (rows of <= 64 columns: one chunk per run)."""
+    ro, ci = a.row_offsets, a.column_indices
+    chunks = 0
+    for t in range(len(bounds) - 1):
+        r, r1 = int(bounds[t][0]), int(bounds[t + 1][0])
+        assert ro[r] == bounds[t][1] and ro[r1] == bounds[t + 1][1]
+        while r < r1:
+            pat = ci[ro[r]:ro[r + 1]]
+            h = 1
+            while r + h < r1 and h < 6:
+                row = ci[ro[r + h]:ro[r + h + 1]]
+                k = min(len(row), len(pat))
+                if not np.array_equal(row[:k], pat[:k]):
+                    break
+                pat = row if len(row) > len(pat) else pat
+                h += 1
+            chunks += 1
+            r += h
+    return chunks
+
+
+def column_runs_per_row(a):
+    """Runs of consecutive columns in each row."""
+    ro, ci = a.row_offsets.astype(np.int64), a.column_indices.astype(np.int64)
+    brk = np.ones(a.num_nonzeros, bool)
+    brk[1:] = np.diff(ci) != 1
+    brk[ro[:-1]] = True
+    return np.add.reduceat(brk.astype(np.int64), ro[:-1])
+
+
+def run_pair(a, seed, runs_env, monkeypatch):
+    if runs_env is None:
+        monkeypatch.delenv("MSPMV_SPMV_RUNS", raising=False)
+    else:
+        monkeypatch.setenv("MSPMV_SPMV_RUNS", runs_env)
+    x = np.random.default_rng(seed).uniform(-1, 1, a.num_cols)
+    with mspmv.GpuCsr(a) as g:
+        plan = g.tile_plan(1)
+        y = g.spmv(x)
+        info = {"kname": g.kernel_name(), "plan": plan, "nb": g.plan_block_tiles(1),
+                "rounds": g.plan_block_rounds(1), "records": g.plan_block_records(1)}
+    return x, y, info
+
+
+def assert_pair_tree(name, a, x, y, info):
+    want = pair_tree_spmv(a, x)
+    bad = np.flatnonzero(y.view(np.uint64) != want.view(np.uint64))
+    print(f"{name}: {info['kname']}, {info['nb']} of {info['plan']['num_tiles']} tiles on node blocks, "
+          f"{info['rounds']} of two rounds, records (compact, escaped) {info['records']}, "
+          f"{bad.size} of {a.num_rows} rows differ")
+    assert info["kname"].startswith("k_spmv_blk<0,") and info["kname"].endswith(",6,false>"), info["kname"]
+    assert bad.size == 0, (bad[:5], y[bad[:5]], want[bad[:5]])
+
+
+@pytest.mark.parametrize("runs_env", [None, "0"])
+def test_compact_records_bit_exact(monkeypatch, runs_env):
+    """Shape 1: rows of 7-10 column-runs; every chunk has a compact record."""
+    a = mspmv.CsrMatrix.synth_fem_blocked(4198, 222000, 6, 60, seed=5)
+    cr = column_runs_per_row(a)
+    assert cr.max() <= 10, np.bincount(cr)
+    x, y, info = run_pair(a, 41, runs_env, monkeypatch)
+    assert_pair_tree(f"shape1-runs{runs_env}", a, x, y, info)
+    assert info["nb"] == info["plan"]["num_tiles"]
+    compact, escaped = info["records"]
+    assert escaped == 0
+    assert compact == count_chunks(a, info["plan"]["bounds"])
+
+
+def test_two_rounds_bit_exact(monkeypatch):
+    """Shape 2: 36 per row on the merge-path plan, tiles of more than 8 chunks: records 8-15."""
+    a = mspmv.CsrMatrix.synth_fem_blocked(4200, 151200, 6, 60, seed=5)
+    x, y, info = run_pair(a, 42, "0", monkeypatch)
+    assert_pair_tree("shape2", a, x, y, info)
+    assert info["rounds"] > 0
+    compact, escaped = info["records"]
+    assert escaped == 0 and compact == count_chunks(a, info["plan"]["bounds"])
+
+
+def test_odd_column_runs_bit_exact(monkeypatch):
+    """Shape 3: nodes of 5 unknowns, column-runs of odd length, so lanes' pairs straddle two runs."""
+    a = mspmv.CsrMatrix.synth_fem_blocked(4200, 210000, 5, 60, seed=5)
+    ro, ci = a.row_offsets.astype(np.int64), a.column_indices.astype(np.int64)
+    pos = np.arange(a.num_nonzeros) - np.repeat(ro[:-1], np.diff(ro))
+    first = (pos % 2 == 0) & (np.arange(a.num_nonzeros) + 1 < np.repeat(ro[1:], np.diff(ro)))
+    straddled = int(np.count_nonzero(ci[np.flatnonzero(first) + 1] != ci[first] + 1))
+    assert straddled > a.num_rows  # more than one such pair per row
+    x, y, info = run_pair(a, 43, None, monkeypatch)
+    assert_pair_tree("shape3", a, x, y, info)
+    assert info["records"][0] > 0 and info["records"][1] == 0
+
+
+def test_mixed_plan_records(monkeypatch, orc):
+    """Shape 4: odd nodes and off-pattern rows (1,250 rows with a pair straddling two column-runs; at this
+    size every tile is still a register run tile), against the oracle."""
+    monkeypatch.delenv("MSPMV_SPMV_RUNS", raising=False)
+    a = mspmv.CsrMatrix.synth_fem_perturbed(4200, 222000, 6, 60, 0.05, 0.02, seed=5)
+    x = np.random.default_rng(44).uniform(-1, 1, a.num_cols)
+    with mspmv.GpuCsr(a) as g:
+        plan = g.tile_plan(1)
+        y = g.spmv(x)
+        kname = g.kernel_name()
+        compact, escaped = g.plan_block_records(1)
+        check_parity(a, y, orc.spmv_gold(a, x), x, plan, 1)
+    print(f"shape4: {kname}, records (compact, escaped) ({compact}, {escaped})")
+    assert kname.startswith("k_spmv_blk<0,"), kname
+    assert compact > 0
+
+
+def test_fallback_tiles_beside_records(monkeypatch, orc):
+    """Shape 1 with 1,200 stencil rows (7 per row, no runs) below it: k_spmv_blk<.., true>, whose tiles
+    without runs have all-zero records (count 0) and take the register fallback."""
+    monkeypatch.delenv("MSPMV_SPMV_RUNS", raising=False)
+    f = mspmv.CsrMatrix.synth_fem_blocked(4198, 222000, 6, 60, seed=5)
+    rng = np.random.default_rng(9)
+    ms = 1200
+    base = rng.integers(0, f.num_cols - 40, ms)
+    ci = (base[:, None] + np.arange(0, 35, 5)[None, :]).astype(np.int32).reshape(-1)
+    ro = np.concatenate([f.row_offsets, f.row_offsets[-1] + np.arange(7, 7 * ms + 1, 7)]).astype(np.int32)
+    a = mspmv.CsrMatrix.from_arrays(f.num_cols, ro, np.concatenate([f.column_indices, ci]),
+                                    np.concatenate([f.values, rng.uniform(0.5, 1.5, 7 * ms)]))
+    x = np.random.default_rng(47).uniform(-1, 1, a.num_cols)
+    with mspmv.GpuCsr(a) as g:
+        plan = g.tile_plan(1)
+        y = g.spmv(x)
+        kname = g.kernel_name()
+        nb = g.plan_block_tiles(1)
+        compact, escaped = g.plan_block_records(1)
+        check_parity(a, y, orc.spmv_gold(a, x), x, plan, 1)
+    print(f"fallback: {kname}, {nb} of {plan['num_tiles']} tiles on node blocks, records ({compact}, {escaped})")
+    assert kname.startswith("k_spmv_blk<0,") and kname.endswith(",6,true>"), kname
+    assert 0 < nb < plan["num_tiles"]
+    assert compact > 0 and escaped == 0
+
+
+def escape_matrix():
+    """Shape 1 with every seventh node's rows on pairs of columns two apart over a window twice as wide:
+    26-27 column-runs, the row lengths and the one list per node kept."""
+    a = mspmv.CsrMatrix.synth_fem_blocked(4198, 222000, 6, 60, seed=5)
+    ro = a.row_offsets.astype(np.int64)
+    ci = a.column_indices.copy()
+    for node in range(0, (a.num_rows + 5) // 6, 7):
+        rows = range(6 * node, min(6 * node + 6, a.num_rows))
+        j = np.arange(max(int(ro[r + 1] - ro[r]) for r in rows))
+        rel = 4 * (j // 2) + (j % 2)
+        start = max(min(int(ci[ro[rows[0]]]), a.num_cols - 1 - int(rel[-1])), 0)
+        for r in rows:  # a shorter row keeps a prefix of the node's list
+            ci[ro[r]:ro[r + 1]] = (start + rel)[: ro[r + 1] - ro[r]]
+    assert ci.max() < a.num_cols
+    return mspmv.CsrMatrix.from_arrays(a.num_cols, a.row_offsets, ci, a.values)
+
+
+def test_escaped_records_bit_exact(monkeypatch):
+    """Shape 5: chunks of 26-27 column-runs escape to the column stream, sharing tiles with compact ones."""
+    a = escape_matrix()
+    cr = column_runs_per_row(a)
+    assert set(np.unique(cr[cr > 12])) <= {26, 27} and np.count_nonzero(cr > 12) >= 600
+    x, y, info = run_pair(a, 45, None, monkeypatch)
+    assert_pair_tree("shape5", a, x, y, info)
+    compact, escaped = info["records"]
+    assert escaped > 0 and compact > escaped
+    assert compact + escaped == count_chunks(a, info["plan"]["bounds"])
+
+
+def test_wide_column_range(monkeypatch, orc):
+    """Shape 6: tiles whose columns span about 60,000: `start` uses its top bit."""
+    monkeypatch.delenv("MSPMV_SPMV_RUNS", raising=False)
+    a = mspmv.CsrMatrix.synth_fem_blocked(66000, 3498000, 6, 5000, seed=5)
+    ro = a.row_offsets.astype(np.int64)
+    span = a.column_indices[ro[1:] - 1].astype(np.int64) - a.column_indices[ro[:-1]]
+    assert span.max() > 40000  # beyond 15 bits within single rows, let alone tiles
+    x = np.random.default_rng(46).uniform(-1, 1, a.num_cols)
+    with mspmv.GpuCsr(a) as g:
+        plan = g.tile_plan(1)
+        y = g.spmv(x)
+        info = {"kname": g.kernel_name(), "plan": plan, "nb": g.plan_block_tiles(1),
+                "rounds": g.plan_block_rounds(1), "records": g.plan_block_records(1)}
+        if info["kname"].endswith(",6,false>"):
+            assert_pair_tree("shape6", a, x, y, info)
+        else:
+            print(f"shape6: {info['kname']}, records {info['records']}")
+            check_parity(a, y, orc.spmv_gold(a, x), x, plan, 1)
+    assert info["kname"].startswith("k_spmv_blk<0,"), info["kname"]
+    assert info["records"][0] > 0
