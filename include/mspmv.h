@@ -360,6 +360,39 @@ MSPMV_API mspmv_status mspmv_dpbicgstab_ilu0_multi_dev(mspmv_handle a, mspmv_ilu
                                                        int L, int max_iters, double tolerance, int *iters,
                                                        double *max_err_hist, int hist_cap);
 
+/* ---- multi-colour IC(0): the same ordering for the block PCG -------------------------- */
+/* The multi-colour IC(0) factor of A itself (not of a factor).  colors == NULL: mspmv_color_greedy's;
+ * colours the caller supplies pass mspmv_ilu0_create_colored's checks (in [0, n), every colour of
+ * 0..C-1 in use, no entry (i, j), i != j, joining two rows of one colour: MSPMV_ERR_INVALID otherwise,
+ * the message naming the first offending row).  Then perm orders the rows stably by colour,
+ * Ap = P A P^T (mspmv_csr_permute_sym), and L is mspmv_ic0_factor of Ap -- with its row checks (a row
+ * without its diagonal is MSPMV_ERR_INVALID, the row named in the colour ordering) and its
+ * diagonal-shift retries (*shift, nullable, receives the shift used; MSPMV_ERR_BREAKDOWN after 20
+ * attempts) -- and L^T is mspmv_csr_transpose of it.  A's own structure is checked as mspmv_ic0_nnz
+ * checks it (square, consistent offsets, columns in range).  All of that happens before the device
+ * is touched.  Uploaded: L (diagonal last in its row), L^T (diagonal first), perm, the colour offsets.
+ * The result is an ordinary mspmv_ic0: mspmv_dpcg_ic0_multi[_dev] takes it unchanged
+ * (mspmv_cg_kernel_name then reads "MC-IC0-PCG (split, S sweeps of C colours)", S = 2 C - 1, and
+ * MSPMV_ERR_STALL cannot occur), mspmv_ic0_destroy frees it.  An apply Z = P^T L^-T L^-1 P R is one
+ * launch per colour and triangle, in stream order; the last colour's rows of L^T hold the diagonal
+ * alone, so its forward launch divides twice (y = (r - s) / d, z = y / d, each rounded) and the
+ * backward sweeps start at colour C - 2: 2 C - 1 launches.  A row's sum runs over the entries before
+ * the diagonal in mspmv_ilu0_create_colored's summation order, so a solve is reproducible against
+ * np.add.reduceat bit for bit.  No reference counterpart; red-black orderings cost iterations. */
+MSPMV_API mspmv_status mspmv_ic0_create_colored(const mspmv_csr_d *a, const int *colors, int device, double *shift,
+                                                mspmv_ic0 *out);
+/* *num_colors: the factor's colours, 0 for a natural-order factor (mspmv_ic0_create); perm (null,
+ * or n entries): row i of the permuted matrix is row perm[i] of A (untouched for 0 colours).
+ * On a multi-colour factor mspmv_ic0_solve_dev solves one triangle of Ap's factor, B and X in the
+ * colour ordering (colours ascending for L, descending for L^T; no pending-pattern fill, no
+ * polling), under the same argument contract. */
+MSPMV_API mspmv_status mspmv_ic0_colors(mspmv_ic0 m, int *num_colors, int *perm);
+/* X = L^-T L^-1 B in A's own ordering, for either kind of factor, on a's stream, synchronised: the
+ * two tagged solves through the factor's intermediate (natural order), or the colour sweeps, which
+ * gather by perm on the way in and scatter on the way out.  mspmv_ilu0_apply_dev's argument
+ * contract, check for check; X is untouched on a rejected call. */
+MSPMV_API mspmv_status mspmv_ic0_apply_dev(mspmv_handle a, mspmv_ic0 m, const double *d_B, double *d_X, int L);
+
 /* ---- measurement helpers (HIP events on the handle's stream) ------------------------ */
 /* Enqueue `reps` back-to-back SpMV (L == 1) or SpMM launches on device buffers and return
  * the average milliseconds per call measured by hipEvents on the handle's stream.

@@ -1877,6 +1877,9 @@ static mspmv_status cg_solve_native(mspmv_handle_s *h, const double *d_b, double
                         : hm      ? "SPAI-PCG (split)"
                         : ic      ? "IC0-PCG (split)"
                                   : "split (p update, SpMM, p.Ap, update)";
+    if (ic && ic->num_colors > 0)  // an apply is 2 C - 1 colour sweeps (mspmv_color.hip)
+        h->last_cg_kernel = "MC-IC0-PCG (split, " + std::to_string(2 * ic->num_colors - 1) + " sweeps of " +
+                            std::to_string(ic->num_colors) + " colours)";
     const int saved_cap = h->hist_cap;
     h->hist_cap = use_cap;  // kernels record only what the caller asked for
     int poison = 0;
@@ -1913,7 +1916,8 @@ static mspmv_status cg_solve_native(mspmv_handle_s *h, const double *d_b, double
             reinterpret_cast<const void *>((intptr_t)L), reinterpret_cast<const void *>((intptr_t)nblk),
             reinterpret_cast<const void *>((intptr_t)use_cap), hm, mplan,
             hm ? (const void *)hm->d_vals : nullptr, ic, ic ? (const void *)ic->d_y : nullptr,
-            ic ? (const void *)ic->d_lva : nullptr,
+            ic ? (const void *)ic->d_lva : nullptr, ic ? (const void *)ic->d_perm : nullptr,
+            reinterpret_cast<const void *>((intptr_t)(ic ? ic->num_colors : 0)),
             reinterpret_cast<const void *>((uintptr_t)(hm ? hm->gen : 0)),
             reinterpret_cast<const void *>((uintptr_t)(ic ? ic->gen : 0)),
             reinterpret_cast<const void *>((intptr_t)K), reinterpret_cast<const void *>((intptr_t)dot_fused)};
@@ -2064,21 +2068,27 @@ static mspmv_status cg_solve_dev(mspmv_handle_s *h, const double *d_b, double *d
         "CG breakdown: p.Ap gave a non-finite alpha in at least one column (frozen; the other columns were solved)");
 }
 
-// The ILU(0) factor's two n x L panels (the apply's intermediate tri.d_y and, for the solver, the hat panel), grown
-// on demand.
-static mspmv_status ilu0_workspace(mspmv_ilu0_s *ilu, size_t elems, bool hat = true)
+// A factor's n x L panels, grown on demand: the apply's intermediate d_y (tri_workspace) and, for the ILU(0)
+// solver, the hat panel besides (ilu0_workspace).
+static mspmv_status tri_workspace(mspmv_ic0_s *t, size_t elems, const char *what)
 {
-    HIP_TRY(hipSetDevice(ilu->tri.device));
-    if (elems > ilu->tri.y_cap) {
-        if (ilu->tri.d_y)
-            (void)hipFree(ilu->tri.d_y);
-        ilu->tri.d_y = nullptr;
-        ilu->tri.y_cap = 0;
-        if (hipMalloc(&ilu->tri.d_y, sizeof(double) * elems) != hipSuccess)
-            return (set_error("ILU(0) workspace allocation failed"), MSPMV_ERR_OOM);
-        ilu->tri.y_cap = elems;
+    HIP_TRY(hipSetDevice(t->device));
+    if (elems > t->y_cap) {
+        if (t->d_y)
+            (void)hipFree(t->d_y);
+        t->d_y = nullptr;
+        t->y_cap = 0;
+        if (hipMalloc(&t->d_y, sizeof(double) * elems) != hipSuccess)
+            return (set_error(std::string(what) + " workspace allocation failed"), MSPMV_ERR_OOM);
+        t->y_cap = elems;
     }
-    if (hat && elems > ilu->hat_cap) {
+    return MSPMV_OK;
+}
+
+static mspmv_status ilu0_workspace(mspmv_ilu0_s *ilu, size_t elems)
+{
+    ST_TRY(tri_workspace(&ilu->tri, elems, "ILU(0)"));
+    if (elems > ilu->hat_cap) {
         dev_free(ilu->d_hat);
         ilu->d_hat = nullptr;
         ilu->hat_cap = 0;
@@ -2136,9 +2146,9 @@ static mspmv_status bicgstab_solve_native(mspmv_handle_s *h, const double *d_b, 
         ST_TRY(ilu0_workspace(ilu, elems));
     const char *name = ilu ? "ILU0-BiCGSTAB" : "BiCGSTAB";
     h->last_cg_kernel = ilu ? "ILU0-BiCGSTAB (2 SpMM + 4 trsv + 5 passes)" : "BiCGSTAB (2 SpMM + 5 passes)";
-    if (ilu && ilu->num_colors > 0)
+    if (ilu && ilu->tri.num_colors > 0)
         h->last_cg_kernel =
-            "MC-ILU0-BiCGSTAB (2 SpMM + 4 sweeps of " + std::to_string(ilu->num_colors) + " colours + 5 passes)";
+            "MC-ILU0-BiCGSTAB (2 SpMM + 4 sweeps of " + std::to_string(ilu->tri.num_colors) + " colours + 5 passes)";
     h->last_solver_product = solver_product_kernel_name(h, *plan, splan, L);
     const int use_cap = hist ? cap : 0;
     const int saved_cap = h->hist_cap;
@@ -2166,9 +2176,9 @@ static mspmv_status bicgstab_solve_native(mspmv_handle_s *h, const double *d_b, 
         if (ilu) {  // the factor, its generation, its value arrays, its workspace
             key.insert(key.end(), {ilu, reinterpret_cast<const void *>((uintptr_t)ilu->tri.gen), ilu->tri.d_lva,
                                    ilu->tri.d_uva, ilu->tri.d_y, ilu->d_hat});
-            if (ilu->num_colors > 0)  // what the colour sweeps read besides: the ordering and the two patterns
-                key.insert(key.end(), {ilu->d_perm, ilu->tri.d_lro, ilu->tri.d_lci, ilu->tri.d_uro, ilu->tri.d_uci,
-                                       reinterpret_cast<const void *>((intptr_t)ilu->num_colors)});
+            if (ilu->tri.num_colors > 0)  // what the colour sweeps read besides: the ordering and the two patterns
+                key.insert(key.end(), {ilu->tri.d_perm, ilu->tri.d_lro, ilu->tri.d_lci, ilu->tri.d_uro, ilu->tri.d_uci,
+                                       reinterpret_cast<const void *>((intptr_t)ilu->tri.num_colors)});
             st = solver_graph(h, SolverGraph{h->pbicg_graph, h->pbicg_exec, h->pbicg_graph_key}, key, K, iterate, name);
             exec = h->pbicg_exec;
         } else {
@@ -2512,6 +2522,7 @@ static void ic0_release(mspmv_ic0_s *m)
     dev_free(m->d_uva);
     dev_free(m->d_fwd_order);
     dev_free(m->d_bwd_order);
+    dev_free(m->d_perm);
     if (m->d_y)
         (void)hipFree(m->d_y);
 }
@@ -2549,8 +2560,7 @@ mspmv_status mspmv_dpcg_ic0_multi(mspmv_handle a, mspmv_ic0 m, const double *B, 
 // One triangular solve with a factor, alone: the pass the preconditioner applies run (launch_ic0_trsv), on a's
 // stream with a's control word, synchronised.  what: "IC(0)" / "ILU(0)"; which_msg: the selector's error text.
 static mspmv_status tri_solve_dev(mspmv_handle a, const mspmv_ic0_s *m, int which, const double *d_B, double *d_X,
-                                  int L, const char *what, const char *which_msg,
-                                  const mspmv_ilu0_s *colored = nullptr)
+                                  int L, const char *what, const char *which_msg)
 {
     ST_TRY(check_handle(a));
     if (!m)
@@ -2573,8 +2583,8 @@ static mspmv_status tri_solve_dev(mspmv_handle a, const mspmv_ic0_s *m, int whic
     if (!a->d_ctrl)
         ST_TRY(dev_alloc(&a->d_ctrl, 1));
     HIP_TRY(hipMemsetAsync(a->d_ctrl, 0, sizeof(CgControl), a->stream));
-    if (colored)  // a multi-colour factor: one sweep per colour, in the colour ordering
-        HIP_TRY(launch_color_trsv(colored, which != 0, d_B, d_X, L, a->d_ctrl, a->stream));
+    if (m->num_colors > 0)  // a multi-colour factor: one sweep per colour, in the colour ordering
+        HIP_TRY(launch_color_trsv(m, which != 0, d_B, d_X, L, a->d_ctrl, a->stream));
     else
         HIP_TRY(launch_ic0_trsv(m, which == 0, d_B, d_X, L, a->d_ctrl, a->stream));
     HIP_TRY(hipStreamSynchronize(a->stream));
@@ -2640,8 +2650,33 @@ mspmv_status mspmv_ilu0_destroy(mspmv_ilu0 m)
         return MSPMV_OK;
     ic0_release(&m->tri);
     dev_free(m->d_hat);
-    dev_free(m->d_perm);
     delete m;
+    return MSPMV_OK;
+}
+
+// The colours of a multi-colour factor whose triangles upload_triangles has placed in t: perm on the device, and per
+// colour the longest row of each triangle in off-diagonal entries (L's rows hold their diagonal when l_diag, U's
+// always), which picks a sweep's LONG instantiation.
+static mspmv_status upload_colors(mspmv_ic0_s *t, std::vector<int> &perm, std::vector<int> &color_off,
+                                  const std::vector<int> &lro, const std::vector<int> &uro, bool l_diag,
+                                  const char *what)
+{
+    const int n = t->n, C = (int)color_off.size() - 1;
+    ST_TRY(dev_alloc(&t->d_perm, (size_t)n));
+    if (n && hipMemcpy(t->d_perm, perm.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess) {
+        set_error(std::string(what) + " upload failed");
+        return MSPMV_ERR_HIP;
+    }
+    t->num_colors = C;
+    t->l_diag = l_diag;
+    t->lmax.assign((size_t)C, 0), t->umax.assign((size_t)C, 0);
+    for (int c = 0; c < C; ++c)
+        for (int i = color_off[c]; i < color_off[(size_t)c + 1]; ++i) {
+            t->lmax[c] = std::max(t->lmax[c], lro[(size_t)i + 1] - lro[i] - (l_diag ? 1 : 0));
+            t->umax[c] = std::max(t->umax[c], uro[(size_t)i + 1] - uro[i] - 1);
+        }
+    t->color_off.swap(color_off);
+    t->perm.swap(perm);
     return MSPMV_OK;
 }
 
@@ -2654,68 +2689,62 @@ mspmv_status mspmv_ilu0_create_colored(const mspmv_csr_d *a, const int *colors, 
     std::vector<int> perm, color_off, lro, lci, uro, uci;
     std::vector<double> lva, uva;
     ST_TRY(ilu0_colored_host(a, colors, perm, color_off, lro, lci, lva, uro, uci, uva));
-    const int n = a->num_rows, C = (int)color_off.size() - 1;
     mspmv_ilu0_s *m = new mspmv_ilu0_s;
-    mspmv_status st = upload_triangles(n, lro.data(), lci.data(), lva.data(), (int)lci.size(), uro.data(), uci.data(),
-                                       uva.data(), (int)uci.size(), device, &m->tri, "ILU(0)");
+    mspmv_status st = upload_triangles(a->num_rows, lro.data(), lci.data(), lva.data(), (int)lci.size(), uro.data(),
+                                       uci.data(), uva.data(), (int)uci.size(), device, &m->tri, "ILU(0)");
     if (st == MSPMV_OK)
-        st = dev_alloc(&m->d_perm, (size_t)n);
-    if (st == MSPMV_OK && n && hipMemcpy(m->d_perm, perm.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess) {
-        set_error("ILU(0) upload failed");
-        st = MSPMV_ERR_HIP;
-    }
+        st = upload_colors(&m->tri, perm, color_off, lro, uro, false, "ILU(0)");
     if (st != MSPMV_OK) {
         mspmv_ilu0_destroy(m);
         return st;
     }
-    m->num_colors = C;
-    m->lmax.assign((size_t)C, 0), m->umax.assign((size_t)C, 0);
-    for (int c = 0; c < C; ++c)
-        for (int i = color_off[c]; i < color_off[(size_t)c + 1]; ++i) {
-            m->lmax[c] = std::max(m->lmax[c], lro[(size_t)i + 1] - lro[i]);
-            m->umax[c] = std::max(m->umax[c], uro[(size_t)i + 1] - uro[i] - 1);
-        }
-    m->color_off.swap(color_off);
-    m->perm.swap(perm);
     *out = m;
+    return MSPMV_OK;
+}
+
+static mspmv_status tri_colors(const mspmv_ic0_s *t, int *num_colors, int *perm, const char *who)
+{
+    if (!t || !num_colors)
+        return invalid(std::string(who) + ": null factor or output");
+    *num_colors = t->num_colors;
+    if (perm && t->num_colors > 0)
+        std::copy(t->perm.begin(), t->perm.end(), perm);
     return MSPMV_OK;
 }
 
 mspmv_status mspmv_ilu0_colors(mspmv_ilu0 m, int *num_colors, int *perm)
 {
-    if (!m || !num_colors)
-        return invalid("ilu0_colors: null factor or output");
-    *num_colors = m->num_colors;
-    if (perm && m->num_colors > 0)
-        std::copy(m->perm.begin(), m->perm.end(), perm);
-    return MSPMV_OK;
+    return tri_colors(m ? &m->tri : nullptr, num_colors, perm, "ilu0_colors");
 }
 
 mspmv_status mspmv_ilu0_solve_dev(mspmv_handle a, mspmv_ilu0 m, int upper, const double *d_B, double *d_X, int L)
 {
     return tri_solve_dev(a, m ? &m->tri : nullptr, upper, d_B, d_X, L, "ILU(0)",
-                         "upper must be 0 (L X = B) or 1 (U X = B)", m && m->num_colors > 0 ? m : nullptr);
+                         "upper must be 0 (L X = B) or 1 (U X = B)");
 }
 
-mspmv_status mspmv_ilu0_apply_dev(mspmv_handle a, mspmv_ilu0 m, const double *d_B, double *d_X, int L)
+// The preconditioner apply with a factor, alone: both triangles through the factor's intermediate, on a's stream
+// with a's control word, synchronised.  what: "IC(0)" / "ILU(0)".
+static mspmv_status tri_apply_dev(mspmv_handle a, mspmv_ic0_s *m, const double *d_B, double *d_X, int L,
+                                  const char *what)
 {
     ST_TRY(check_handle(a));
     if (!m)
-        return invalid("null ILU(0) factor");
-    if (a->m != a->n || m->tri.n != a->m || m->tri.device != a->device)
-        return invalid("the ILU(0) factor must match the matrix's shape and device");
+        return invalid(std::string("null ") + what + " factor");
+    if (a->m != a->n || m->n != a->m || m->device != a->device)
+        return invalid(std::string("the ") + what + " factor must match the matrix's shape and device");
     if (!supported_L(L))
         return (set_error("L must be one of 1, 2, 4, 8, 16"), MSPMV_ERR_UNSUPPORTED);
-    if (m->tri.n == 0)
+    if (m->n == 0)
         return MSPMV_OK;
     if (!d_B || !d_X)
         return invalid("null panel");
     if (!aligned16(d_B) || !aligned16(d_X))
         return invalid("preconditioner-apply panels must be 16-byte aligned");
-    const uintptr_t b0 = (uintptr_t)d_B, x0 = (uintptr_t)d_X, bytes = sizeof(double) * (size_t)m->tri.n * L;
+    const uintptr_t b0 = (uintptr_t)d_B, x0 = (uintptr_t)d_X, bytes = sizeof(double) * (size_t)m->n * L;
     if (b0 < x0 + bytes && x0 < b0 + bytes)
         return invalid("preconditioner-apply panels must not overlap");
-    ST_TRY(ilu0_workspace(m, (size_t)m->tri.n * L, false));  // the intermediate tri.d_y alone
+    ST_TRY(tri_workspace(m, (size_t)m->n * L, what));  // the intermediate d_y
     HIP_TRY(hipSetDevice(a->device));
     if (!a->d_ctrl)
         ST_TRY(dev_alloc(&a->d_ctrl, 1));
@@ -2723,17 +2752,56 @@ mspmv_status mspmv_ilu0_apply_dev(mspmv_handle a, mspmv_ilu0 m, const double *d_
     if (m->num_colors > 0) {
         HIP_TRY(launch_color_apply(m, d_B, d_X, L, a->d_ctrl, a->stream));
     } else {
-        HIP_TRY(launch_ic0_trsv(&m->tri, true, d_B, m->tri.d_y, L, a->d_ctrl, a->stream));
-        HIP_TRY(launch_ic0_trsv(&m->tri, false, m->tri.d_y, d_X, L, a->d_ctrl, a->stream));
+        HIP_TRY(launch_ic0_trsv(m, true, d_B, m->d_y, L, a->d_ctrl, a->stream));
+        HIP_TRY(launch_ic0_trsv(m, false, m->d_y, d_X, L, a->d_ctrl, a->stream));
     }
     HIP_TRY(hipStreamSynchronize(a->stream));
     CgControl fin{};
     HIP_TRY(hipMemcpy(&fin, a->d_ctrl, sizeof(CgControl), hipMemcpyDeviceToHost));
     if (fin.breakdown == 2) {
-        set_error("ILU(0) apply: a triangular-solve dependency never became ready (solve stalled)");
+        set_error(std::string(what) + " apply: a triangular-solve dependency never became ready (solve stalled)");
         return MSPMV_ERR_STALL;
     }
     return MSPMV_OK;
+}
+
+mspmv_status mspmv_ilu0_apply_dev(mspmv_handle a, mspmv_ilu0 m, const double *d_B, double *d_X, int L)
+{
+    return tri_apply_dev(a, m ? &m->tri : nullptr, d_B, d_X, L, "ILU(0)");
+}
+
+// ---- multi-colour IC(0) ----------------------------------------------------------------------
+mspmv_status mspmv_ic0_create_colored(const mspmv_csr_d *a, const int *colors, int device, double *shift,
+                                      mspmv_ic0 *out)
+{
+    if (!out)
+        return invalid("null output");
+    *out = nullptr;
+    // the checks, the ordering and the factorisation: all on the host, before the device is touched
+    std::vector<int> perm, color_off, lro, lci, uro, uci;
+    std::vector<double> lva, uva;
+    ST_TRY(ic0_colored_host(a, colors, perm, color_off, lro, lci, lva, uro, uci, uva, shift));
+    mspmv_ic0_s *m = new mspmv_ic0_s;
+    mspmv_status st = upload_triangles(a->num_rows, lro.data(), lci.data(), lva.data(), (int)lci.size(), uro.data(),
+                                       uci.data(), uva.data(), (int)uci.size(), device, m, "IC(0)");
+    if (st == MSPMV_OK)
+        st = upload_colors(m, perm, color_off, lro, uro, true, "IC(0)");
+    if (st != MSPMV_OK) {
+        mspmv_ic0_destroy(m);
+        return st;
+    }
+    *out = m;
+    return MSPMV_OK;
+}
+
+mspmv_status mspmv_ic0_colors(mspmv_ic0 m, int *num_colors, int *perm)
+{
+    return tri_colors(m, num_colors, perm, "ic0_colors");
+}
+
+mspmv_status mspmv_ic0_apply_dev(mspmv_handle a, mspmv_ic0 m, const double *d_B, double *d_X, int L)
+{
+    return tri_apply_dev(a, m, d_B, d_X, L, "IC(0)");
 }
 
 // ---- measurement ---------------------------------------------------------------------------

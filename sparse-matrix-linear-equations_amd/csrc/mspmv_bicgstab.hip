@@ -467,8 +467,8 @@ hipError_t launch_bicgstab_iteration(mspmv_handle_s *h, const TilePlan &plan, co
 // pending-pattern fill overwrites it first).
 static hipError_t ilu0_apply(mspmv_handle_s *h, mspmv_ilu0_s *ilu, int L, const double *src, double *dst)
 {
-    if (ilu->num_colors > 0)  // a multi-colour factor: 2 C colour sweeps, no fill (mspmv_color.hip)
-        return launch_color_apply(ilu, src, dst, L, h->d_ctrl, h->stream);
+    if (ilu->tri.num_colors > 0)  // a multi-colour factor: 2 C colour sweeps, no fill (mspmv_color.hip)
+        return launch_color_apply(&ilu->tri, src, dst, L, h->d_ctrl, h->stream);
     hipError_t e = launch_ic0_trsv(&ilu->tri, true, src, ilu->tri.d_y, L, h->d_ctrl, h->stream);
     if (e == hipSuccess)
         e = launch_ic0_trsv(&ilu->tri, false, ilu->tri.d_y, dst, L, h->d_ctrl, h->stream);

@@ -1108,9 +1108,12 @@ hipError_t launch_ic0_trsv(const mspmv_ic0_s *ic, bool fwd, const double *d_b, d
 }
 
 // Z = L^-T (L^-1 R): ForwardSolveMultiple into ic->d_y, then BackwardSolveMultiple
-// (incomplete_cholesky.hpp:89-92, :166-167), each into a panel pre-filled with the pending pattern.
+// (incomplete_cholesky.hpp:89-92, :166-167), each into a panel pre-filled with the pending pattern.  A multi-colour
+// factor: 2 C - 1 colour sweeps through ic->d_y, no fill (mspmv_color.hip).
 static hipError_t ic0_apply(mspmv_handle_s *h, mspmv_ic0_s *ic, int L, const double *r, double *z)
 {
+    if (ic->num_colors > 0)
+        return launch_color_apply(ic, r, z, L, h->d_ctrl, h->stream);
     hipError_t e = launch_ic0_trsv(ic, true, r, ic->d_y, L, h->d_ctrl, h->stream);
     if (e == hipSuccess)
         e = launch_ic0_trsv(ic, false, ic->d_y, z, L, h->d_ctrl, h->stream);

@@ -1,5 +1,5 @@
-// mspmv_color.cpp -- multi-colour ordering for ILU(0), on the host (mspmv_ilu0_create_colored).  No reference
-// counterpart.
+// mspmv_color.cpp -- multi-colour ordering for ILU(0) and IC(0), on the host (mspmv_ilu0_create_colored,
+// mspmv_ic0_create_colored).  No reference counterpart.
 //
 //   * mspmv_color_greedy: rows 0..n-1 in turn take the smallest colour no already-coloured neighbour holds, the
 //     neighbours being those of A + A^T's off-diagonal pattern (stored zeros count).  Sequential, deterministic.
@@ -8,6 +8,8 @@
 //     mspmv_ilu0_values -> L (strictly lower, unit diagonal implied) and U (diagonal first).  Rows of one colour
 //     share no entry, so row i of L reads only rows of earlier colours and row i of U only rows of later ones: a
 //     colour is one independent sweep (k_trsv_color, mspmv_color.hip), the factor has at most C levels.
+//   * ic0_colored_host: the same colours, perm and Ap (color_order, shared) -> mspmv_ic0_factor of Ap, diagonal
+//     shifts included -> L (diagonal last) and L^T by mspmv_csr_transpose (diagonal first).
 // Everything here runs before the device is touched.
 #include "mspmv.h"
 
@@ -23,6 +25,10 @@ mspmv_status ilu0_colored_host(const mspmv_csr_d *a, const int *colors, std::vec
                                std::vector<int> &color_off, std::vector<int> &lro, std::vector<int> &lci,
                                std::vector<double> &lva, std::vector<int> &uro, std::vector<int> &uci,
                                std::vector<double> &uva);
+mspmv_status ic0_colored_host(const mspmv_csr_d *a, const int *colors, std::vector<int> &perm,
+                              std::vector<int> &color_off, std::vector<int> &lro, std::vector<int> &lci,
+                              std::vector<double> &lva, std::vector<int> &uro, std::vector<int> &uci,
+                              std::vector<double> &uva, double *shift);
 }
 
 static mspmv_status invalid(const std::string &msg)
@@ -140,15 +146,12 @@ extern "C" MSPMV_API mspmv_status mspmv_csr_permute_sym(const mspmv_csr_d *a, co
     return MSPMV_OK;
 }
 
-mspmv_status mspmv::ilu0_colored_host(const mspmv_csr_d *a, const int *colors, std::vector<int> &perm,
-                                      std::vector<int> &color_off, std::vector<int> &lro, std::vector<int> &lci,
-                                      std::vector<double> &lva, std::vector<int> &uro, std::vector<int> &uci,
-                                      std::vector<double> &uva)
+// Colours (given and checked, or greedy) -> perm (rows stably sorted by colour) -> Ap = P A P^T into pro, pci, pva.
+// a: square with consistent offsets and columns in range; who prefixes the messages.
+static mspmv_status color_order(const mspmv_csr_d *a, const int *colors, const char *who, std::vector<int> &perm,
+                                std::vector<int> &color_off, std::vector<int> &pro, std::vector<int> &pci,
+                                std::vector<double> &pva)
 {
-    const char *who = "ilu0_create_colored";
-    mspmv_status st = ilu0_check_rows(a, who);
-    if (st != MSPMV_OK)
-        return st;
     const int n = a->num_rows, nnz = a->num_nonzeros;
     std::vector<int> col((size_t)n, 0);
     int num = 0;
@@ -196,9 +199,26 @@ mspmv_status mspmv::ilu0_colored_host(const mspmv_csr_d *a, const int *colors, s
             perm[inv[i]] = i;
         }
     }
-    std::vector<int> pro((size_t)n + 1, 0), pci((size_t)std::max(nnz, 1));
-    std::vector<double> pva((size_t)std::max(nnz, 1)), lu((size_t)std::max(nnz, 1));
+    pro.assign((size_t)n + 1, 0), pci.assign((size_t)std::max(nnz, 1), 0), pva.assign((size_t)std::max(nnz, 1), 0.0);
     permute(a, perm.data(), inv, pro.data(), pci.data(), pva.data());
+    return MSPMV_OK;
+}
+
+mspmv_status mspmv::ilu0_colored_host(const mspmv_csr_d *a, const int *colors, std::vector<int> &perm,
+                                      std::vector<int> &color_off, std::vector<int> &lro, std::vector<int> &lci,
+                                      std::vector<double> &lva, std::vector<int> &uro, std::vector<int> &uci,
+                                      std::vector<double> &uva)
+{
+    const char *who = "ilu0_create_colored";
+    mspmv_status st = ilu0_check_rows(a, who);
+    if (st != MSPMV_OK)
+        return st;
+    const int n = a->num_rows, nnz = a->num_nonzeros;
+    std::vector<int> pro, pci;
+    std::vector<double> pva, lu((size_t)std::max(nnz, 1));
+    st = color_order(a, colors, who, perm, color_off, pro, pci, pva);
+    if (st != MSPMV_OK)
+        return st;
     mspmv_csr_d ap = *a;
     ap.row_offsets = pro.data();
     ap.column_indices = pci.data();
@@ -222,4 +242,47 @@ mspmv_status mspmv::ilu0_colored_host(const mspmv_csr_d *a, const int *colors, s
         uro[(size_t)i + 1] = (int)uci.size();
     }
     return MSPMV_OK;
+}
+
+// A's structure by mspmv_ic0_nnz's checks (square, consistent offsets, columns in range: all the colouring and the
+// permutation need); the rows by mspmv_ic0_factor's own, on the permuted matrix, with its diagonal-shift retries.
+mspmv_status mspmv::ic0_colored_host(const mspmv_csr_d *a, const int *colors, std::vector<int> &perm,
+                                     std::vector<int> &color_off, std::vector<int> &lro, std::vector<int> &lci,
+                                     std::vector<double> &lva, std::vector<int> &uro, std::vector<int> &uci,
+                                     std::vector<double> &uva, double *shift)
+{
+    const char *who = "ic0_create_colored";
+    int lnnz = 0;
+    mspmv_status st = mspmv_ic0_nnz(a, &lnnz);  // for its checks: L's count is the permuted matrix's, taken below
+    if (st != MSPMV_OK)
+        return st;
+    const int n = a->num_rows;
+    std::vector<int> pro, pci;
+    std::vector<double> pva;
+    st = color_order(a, colors, who, perm, color_off, pro, pci, pva);
+    if (st != MSPMV_OK)
+        return st;
+    mspmv_csr_d ap = *a;
+    ap.row_offsets = pro.data();
+    ap.column_indices = pci.data();
+    ap.values = pva.data();
+    st = mspmv_ic0_nnz(&ap, &lnnz);
+    if (st != MSPMV_OK)
+        return st;
+    lro.assign((size_t)n + 1, 0), uro.assign((size_t)n + 1, 0);
+    lci.assign((size_t)std::max(lnnz, 1), 0), uci.assign((size_t)std::max(lnnz, 1), 0);
+    lva.assign((size_t)std::max(lnnz, 1), 0.0), uva.assign((size_t)std::max(lnnz, 1), 0.0);
+    st = mspmv_ic0_factor(&ap, lro.data(), lci.data(), lva.data(), shift);
+    if (st != MSPMV_OK) {
+        set_error(std::string(mspmv_last_error()) + " [ic0_create_colored: rows numbered in the colour ordering]");
+        return st;
+    }
+    mspmv_csr_d l = ap;
+    l.num_nonzeros = lnnz;
+    l.row_offsets = lro.data();
+    l.column_indices = lci.data();
+    l.values = lva.data();
+    st = mspmv_csr_transpose(&l, uro.data(), uci.data(), uva.data());
+    lci.resize((size_t)lnnz), lva.resize((size_t)lnnz), uci.resize((size_t)lnnz), uva.resize((size_t)lnnz);
+    return st;
 }

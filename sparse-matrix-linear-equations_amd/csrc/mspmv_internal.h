@@ -356,6 +356,11 @@ struct PatternScope {
 
 // IC(0) factor on the device (mspmv_ic0_create): L and its transpose for the two sync-free
 // triangular solves of the preconditioner apply, their level orders and the intermediate Y.
+// A multi-colour factor (mspmv_ic0_create_colored, mspmv_ilu0_create_colored) is the factor of Ap = P A P^T in
+// the same slots, rows of a colour contiguous (the level orders upload_triangles builds are not used): colour c's
+// rows are [color_off[c], color_off[c + 1]), row i of Ap is row perm[i] of A.  Its solves are one k_trsv_color
+// launch per colour (mspmv_color.hip), never k_trsv_tagged.  IC(0) keeps L's diagonal, last in its row (l_diag);
+// ILU(0) keeps L strictly lower, its unit diagonal implied.
 struct mspmv_ic0_s {
     unsigned long long gen = mspmv_next_generation();
     int device = 0;
@@ -369,24 +374,23 @@ struct mspmv_ic0_s {
     int levels_fwd = 0, levels_bwd = 0;
     double *d_y = nullptr;                   // [n * L] forward-solve result
     size_t y_cap = 0;
+    int num_colors = 0;                      // 0: a natural-order factor
+    bool l_diag = false;                     // multi-colour: L's rows end in their diagonal (IC(0)), else it is implied
+    std::vector<int> color_off, perm;
+    std::vector<int> lmax, umax;             // [C] the colour's longest row of L and of U, in off-diagonal entries
+    int *d_perm = nullptr;
 };
 
 // ILU(0) factor on the device (mspmv_ilu0_create): two different triangles in mspmv_ic0_s's slots -- L (A's
 // strictly lower entries, then an explicit 1.0 diagonal, so k_trsv_tagged divides by 1.0 exactly) where IC(0)
 // keeps its L, and U (diagonal first) where IC(0) keeps L^T -- so launch_ic0_trsv runs unchanged; tri.d_y is
 // the intermediate of an apply.  A type of its own: a nonsymmetric factor is no argument of the PCG.
-// A multi-colour factor (mspmv_ilu0_create_colored) is the ILU(0) of Ap = P A P^T in the same slots, rows of a
-// colour contiguous: L without its unit diagonal, U diagonal first (the level orders upload_triangles builds are
-// not used); colour c's rows are [color_off[c], color_off[c + 1]), row i of Ap is row perm[i] of A.  Its solves
-// are one k_trsv_color launch per colour (mspmv_color.hip), never k_trsv_tagged.
+// A multi-colour factor (mspmv_ilu0_create_colored) keeps L without its unit diagonal and U diagonal first, the
+// colours in tri.
 struct mspmv_ilu0_s {
     mspmv_ic0_s tri;
     double *d_hat = nullptr;  // [n * L] Phat, then Shat, of the running iteration (mspmv_bicgstab.hip)
     size_t hat_cap = 0;
-    int num_colors = 0;       // 0: a natural-order factor
-    std::vector<int> color_off, perm;
-    std::vector<int> lmax, umax;  // [C] the longest row of the colour, in off-diagonal entries, of L and of U
-    int *d_perm = nullptr;
 };
 
 namespace mspmv {
@@ -397,13 +401,21 @@ mspmv_status ilu0_colored_host(const mspmv_csr_d *a, const int *colors, std::vec
                                std::vector<int> &color_off, std::vector<int> &lro, std::vector<int> &lci,
                                std::vector<double> &lva, std::vector<int> &uro, std::vector<int> &uci,
                                std::vector<double> &uva);
+// The host side of mspmv_ic0_create_colored: the same colour checks and ordering, then mspmv_ic0_factor of the
+// permuted matrix (L, diagonal last) and its mspmv_csr_transpose (diagonal first); *shift (nullable): the shift used.
+mspmv_status ic0_colored_host(const mspmv_csr_d *a, const int *colors, std::vector<int> &perm,
+                              std::vector<int> &color_off, std::vector<int> &lro, std::vector<int> &lci,
+                              std::vector<double> &lva, std::vector<int> &uro, std::vector<int> &uci,
+                              std::vector<double> &uva, double *shift);
 // One triangle of a multi-colour factor, in the colour ordering: X = L^-1 B (colours ascending) or U^-1 B
 // (descending), one launch per colour on s.  B and X are distinct panels.
-hipError_t launch_color_trsv(const mspmv_ilu0_s *ilu, bool upper, const double *d_b, double *d_x, int L,
+hipError_t launch_color_trsv(const mspmv_ic0_s *t, bool upper, const double *d_b, double *d_x, int L,
                              const CgControl *ctrl, hipStream_t s);
-// dst = P^T U^-1 L^-1 P src, in A's own ordering, through tri.d_y (n x L): the forward sweeps gather src by perm
-// into d_y, the backward sweeps run in place on d_y and scatter into dst; 2 C launches.
-hipError_t launch_color_apply(const mspmv_ilu0_s *ilu, const double *d_src, double *d_dst, int L,
+// dst = P^T U^-1 L^-1 P src, in A's own ordering, through t->d_y (n x L): the forward sweeps gather src by perm
+// into d_y, the backward sweeps run in place on d_y and scatter into dst.  ILU(0): 2 C launches.  IC(0) (l_diag):
+// 2 C - 1, the last colour's forward launch dividing by the diagonal twice and scattering (its rows of L^T hold
+// the diagonal alone).
+hipError_t launch_color_apply(const mspmv_ic0_s *t, const double *d_src, double *d_dst, int L,
                               const CgControl *ctrl, hipStream_t s);
 
 // Square, consistent CSR whose rows ascend strictly and hold their diagonal (mspmv_ilu0.cpp); else

@@ -111,6 +111,9 @@ _SIGS = {
     "mspmv_dpcg_ic0_multi": (_I, [_P, _P, _P, _P, _I, _I, _D, _I, _PI, _P, _I]),
     "mspmv_dpcg_ic0_multi_dev": (_I, [_P, _P, _P, _P, _I, _I, _D, _I, _PI, _P, _I]),
     "mspmv_ic0_solve_dev": (_I, [_P, _P, _I, _P, _P, _I]),
+    "mspmv_ic0_create_colored": (_I, [ctypes.POINTER(_CsrD), _P, _I, _PD, ctypes.POINTER(_P)]),
+    "mspmv_ic0_colors": (_I, [_P, _PI, _P]),
+    "mspmv_ic0_apply_dev": (_I, [_P, _P, _P, _P, _I]),
     "mspmv_ilu0_values": (_I, [ctypes.POINTER(_CsrD), _P]),
     "mspmv_ilu0_create": (_I, [ctypes.POINTER(_CsrD), _I, ctypes.POINTER(_P)]),
     "mspmv_ilu0_destroy": (_I, [_P]),
@@ -722,14 +725,75 @@ def csr_transpose(a: CsrMatrix) -> CsrMatrix:
 
 
 class GpuIc0:
-    """An IC(0) factor L (and L^T) resident on a device for the GPU triangular solves."""
+    """An IC(0) factor L (and L^T) resident on a device for the GPU triangular solves.  GpuIc0.colored(A) builds
+    the multi-colour factor of A itself, whose solves are one parallel sweep per colour."""
 
     def __init__(self, l: CsrMatrix, device: int = 0):
         h = ctypes.c_void_p()
         _check(lib.mspmv_ic0_create(ctypes.byref(l._c()), device, ctypes.byref(h)), "ic0_create")
         self.h = h.value
         self.device = device
+        self.num_rows = l.num_rows
+        self.shift = None  # known to whoever factored l
         _track(self)
+
+    @classmethod
+    def colored(cls, a: CsrMatrix, colors=None, device: int = 0) -> "GpuIc0":
+        """The multi-colour IC(0) factor of A (mspmv_ic0_create_colored): `colors` [n] (None: color_greedy's)
+        orders the rows colour after colour, and the factor is ic0_factor of the permuted matrix (.shift: the
+        diagonal shift it used).  Every check and the factorisation run on the host before the device is touched."""
+        if colors is not None:
+            colors = np.ascontiguousarray(colors, np.int32)
+            if colors.shape != (a.num_rows,):
+                raise ValueError("colors must hold one colour per row")
+        h = ctypes.c_void_p()
+        sh = ctypes.c_double()
+        _check(lib.mspmv_ic0_create_colored(ctypes.byref(a._c()), None if colors is None else _ptr(colors), device,
+                                            ctypes.byref(sh), ctypes.byref(h)), "ic0_create_colored")
+        self = cls.__new__(cls)
+        self.h = h.value
+        self.device = device
+        self.num_rows = a.num_rows
+        self.shift = sh.value
+        _track(self)
+        return self
+
+    @property
+    def num_colors(self) -> int:
+        """The factor's colours; 0 for a natural-order factor."""
+        num = ctypes.c_int()
+        _check(lib.mspmv_ic0_colors(self.h, ctypes.byref(num), None), "ic0_colors")
+        return num.value
+
+    @property
+    def perm(self):
+        """Row i of the permuted matrix is row perm[i] of A (int32 [n]); None for a natural-order factor."""
+        if self.num_colors == 0:
+            return None
+        num = ctypes.c_int()
+        perm = np.zeros(max(self.num_rows, 1), np.int32)
+        _check(lib.mspmv_ic0_colors(self.h, ctypes.byref(num), _ptr(perm)), "ic0_colors")
+        return perm[: self.num_rows]
+
+    def apply_dev(self, g: "GpuCsr", dB: "DeviceBuffer", dX: "DeviceBuffer", L: int) -> int:
+        """mspmv_ic0_apply_dev on device panels: X = L^-T L^-1 B in A's own ordering."""
+        return _check(lib.mspmv_ic0_apply_dev(g.h, self.h, dB.ptr, dX.ptr, L), "ic0_apply_dev")
+
+    def apply(self, g: "GpuCsr", B: np.ndarray) -> np.ndarray:
+        """The preconditioner apply X = M^-1 B on g's stream (mspmv_ic0_apply_dev), for either kind of factor:
+        a host panel B [n] or [n, L], L in SUPPORTED_L, in A's own ordering."""
+        B = np.ascontiguousarray(B, np.float64)
+        shape = B.shape
+        if B.ndim == 1:
+            B = B[:, None]
+        dB = DeviceBuffer.from_array(B, self.device) if B.size else DeviceBuffer(16, self.device)
+        dX = DeviceBuffer(max(B.nbytes, 16), self.device)
+        try:
+            self.apply_dev(g, dB, dX, B.shape[1])
+            return dX.download(B.shape).reshape(shape)
+        finally:
+            dB.free()
+            dX.free()
 
     def solve_dev(self, g: "GpuCsr", dB: "DeviceBuffer", dX: "DeviceBuffer", L: int, transpose: bool = False) -> int:
         """mspmv_ic0_solve_dev on device panels: one triangular solve, L X = B or L^T X = B."""
@@ -737,7 +801,8 @@ class GpuIc0:
 
     def solve(self, g: "GpuCsr", B: np.ndarray, transpose: bool = False) -> np.ndarray:
         """One triangular solve with the factor on g's stream (mspmv_ic0_solve_dev): X with L X = B, or
-        L^T X = B (transpose), for a host panel B [n] or [n, L], L in SUPPORTED_L."""
+        L^T X = B (transpose), for a host panel B [n] or [n, L], L in SUPPORTED_L.  On a multi-colour factor the
+        triangle is the permuted matrix's, B and X in the colour ordering."""
         B = np.ascontiguousarray(B, np.float64)
         shape = B.shape
         if B.ndim == 1:
