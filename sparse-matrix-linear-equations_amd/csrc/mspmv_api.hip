@@ -1,5 +1,6 @@
 // mspmv_api.hip -- the C-ABI (include/mspmv.h): matrix handles, tile plans, SpMV/SpMM
-// entry points, and the CG drivers.  Host C++17 over the HIP runtime.
+// entry points, and the CG drivers (the IC(0) / ILU(0) factor objects: mspmv_tri.hip).  Host C++17
+// over the HIP runtime.
 #include "mspmv_internal.h"
 
 #include <algorithm>
@@ -31,51 +32,6 @@ unsigned long long mspmv_next_generation()
 }
 
 using namespace mspmv;
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t _e = (expr);                                                                    \
-        if (_e != hipSuccess) {                                                                    \
-            set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                          \
-            return (_e == hipErrorOutOfMemory) ? MSPMV_ERR_OOM : MSPMV_ERR_HIP;                    \
-        }                                                                                          \
-    } while (0)
-
-#define ST_TRY(expr)                                                                               \
-    do {                                                                                           \
-        mspmv_status _s = (expr);                                                                  \
-        if (_s != MSPMV_OK)                                                                        \
-            return _s;                                                                             \
-    } while (0)
-
-static mspmv_status invalid(const std::string &msg)
-{
-    set_error(msg);
-    return MSPMV_ERR_INVALID;
-}
-
-template <typename T>
-static mspmv_status dev_alloc(T **p, size_t count)
-{
-    *p = nullptr;
-    if (count == 0)
-        count = 1;
-    hipError_t e = hipMalloc((void **)p, count * sizeof(T));
-    if (e != hipSuccess) {
-        set_error(std::string("hipMalloc(") + std::to_string(count * sizeof(T)) + " B): " + hipGetErrorString(e));
-        *p = nullptr;
-        return e == hipErrorOutOfMemory ? MSPMV_ERR_OOM : MSPMV_ERR_HIP;
-    }
-    return MSPMV_OK;
-}
-
-template <typename T>
-static void dev_free(T *&p)
-{
-    if (p)
-        (void)hipFree((void *)p);
-    p = nullptr;
-}
 
 __global__ void k_check_cols(const int *__restrict__ cols, long long nnz, int n, int *bad)
 {
@@ -883,19 +839,6 @@ mspmv_status plan_for(mspmv_handle_s *h, int L, const TilePlan **out) { return g
 mspmv_status dia_plan_for(mspmv_handle_s *h, int L, const TilePlan **out) { return dia_plan(h, out, L); }
 }  // namespace mspmv
 
-static mspmv_status validate_host_csr(const mspmv_csr_d *a)
-{
-    if (!a)
-        return invalid("null matrix");
-    if (a->num_rows < 0 || a->num_cols < 0 || a->num_nonzeros < 0)
-        return invalid("negative dimension");
-    if ((long long)a->num_rows + a->num_nonzeros > 0x7fffffffLL)
-        return invalid("num_rows + num_nonzeros must fit in int32 (merge-path diagonals)");
-    if (!a->row_offsets || (a->num_nonzeros > 0 && (!a->column_indices || !a->values)))
-        return invalid("null CSR array");
-    return MSPMV_OK;
-}
-
 static mspmv_status check_offsets_host(const int *ro, int m, int nnz)
 {
     if (ro[0] != 0)
@@ -1049,16 +992,6 @@ static mspmv_status create_common(const mspmv_csr_d *a, int device, bool from_de
     *out = h;
     return MSPMV_OK;
 }
-
-static mspmv_status check_handle(mspmv_handle h)
-{
-    if (!h)
-        return invalid("null handle");
-    HIP_TRY(hipSetDevice(h->device));
-    return MSPMV_OK;
-}
-
-static bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 
 extern "C" {
 
@@ -1806,16 +1739,8 @@ static mspmv_status cg_solve_native(mspmv_handle_s *h, const double *d_b, double
         return invalid("the preconditioner must match the matrix's shape and device");
     if (ic && (ic->n != h->m || ic->device != h->device))
         return invalid("the IC(0) factor must match the matrix's shape and device");
-    if (ic && (size_t)h->m * L > ic->y_cap) {
-        if (ic->d_y)
-            (void)hipFree(ic->d_y);
-        ic->d_y = nullptr;
-        ic->y_cap = 0;
-        HIP_TRY(hipSetDevice(h->device));
-        if (hipMalloc(&ic->d_y, sizeof(double) * (size_t)h->m * L) != hipSuccess)
-            return (set_error("IC(0) workspace allocation failed"), MSPMV_ERR_OOM);
-        ic->y_cap = (size_t)h->m * L;
-    }
+    if (ic)  // the apply's intermediate lives with the factor: grown here, before any capture
+        ST_TRY(tri_workspace(ic, (size_t)h->m * L, "IC(0)"));
     if (!supported_L(L))
         return (set_error("L must be one of 1, 2, 4, 8, 16"), MSPMV_ERR_UNSUPPORTED);
     if (max_iters < 0)
@@ -1910,17 +1835,16 @@ static mspmv_status cg_solve_native(mspmv_handle_s *h, const double *d_b, double
         const void *tk = nullptr;
         static_assert(sizeof(tk) == sizeof(tol), "tolerance bits as a key word");
         std::memcpy(&tk, &tol, sizeof tk);
-        const std::vector<const void *> key = {
+        std::vector<const void *> key = {
             d_x, h->d_r, h->d_p0, h->d_p1, h->d_ap, h->d_partials, h->d_partials_b, h->d_gtickets, h->d_scal,
             h->d_conv, h->d_red, h->d_ctrl, h->d_hist, h->stream, plan, splan, tk,
             reinterpret_cast<const void *>((intptr_t)L), reinterpret_cast<const void *>((intptr_t)nblk),
             reinterpret_cast<const void *>((intptr_t)use_cap), hm, mplan,
-            hm ? (const void *)hm->d_vals : nullptr, ic, ic ? (const void *)ic->d_y : nullptr,
-            ic ? (const void *)ic->d_lva : nullptr, ic ? (const void *)ic->d_perm : nullptr,
-            reinterpret_cast<const void *>((intptr_t)(ic ? ic->num_colors : 0)),
+            hm ? (const void *)hm->d_vals : nullptr,
             reinterpret_cast<const void *>((uintptr_t)(hm ? hm->gen : 0)),
-            reinterpret_cast<const void *>((uintptr_t)(ic ? ic->gen : 0)),
             reinterpret_cast<const void *>((intptr_t)K), reinterpret_cast<const void *>((intptr_t)dot_fused)};
+        if (ic)
+            tri_graph_key(ic, key);
         st = solver_graph(h, SolverGraph{h->cg_graph, h->cg_exec, h->cg_graph_key}, key, K, iterate, "CG");
         exec = h->cg_exec;
     }
@@ -2068,36 +1992,6 @@ static mspmv_status cg_solve_dev(mspmv_handle_s *h, const double *d_b, double *d
         "CG breakdown: p.Ap gave a non-finite alpha in at least one column (frozen; the other columns were solved)");
 }
 
-// A factor's n x L panels, grown on demand: the apply's intermediate d_y (tri_workspace) and, for the ILU(0)
-// solver, the hat panel besides (ilu0_workspace).
-static mspmv_status tri_workspace(mspmv_ic0_s *t, size_t elems, const char *what)
-{
-    HIP_TRY(hipSetDevice(t->device));
-    if (elems > t->y_cap) {
-        if (t->d_y)
-            (void)hipFree(t->d_y);
-        t->d_y = nullptr;
-        t->y_cap = 0;
-        if (hipMalloc(&t->d_y, sizeof(double) * elems) != hipSuccess)
-            return (set_error(std::string(what) + " workspace allocation failed"), MSPMV_ERR_OOM);
-        t->y_cap = elems;
-    }
-    return MSPMV_OK;
-}
-
-static mspmv_status ilu0_workspace(mspmv_ilu0_s *ilu, size_t elems)
-{
-    ST_TRY(tri_workspace(&ilu->tri, elems, "ILU(0)"));
-    if (elems > ilu->hat_cap) {
-        dev_free(ilu->d_hat);
-        ilu->d_hat = nullptr;
-        ilu->hat_cap = 0;
-        ST_TRY(dev_alloc(&ilu->d_hat, elems));
-        ilu->hat_cap = elems;
-    }
-    return MSPMV_OK;
-}
-
 // BiCGSTAB on a panel of native width (mspmv_bicgstab.hip), by cg_solve_native's protocol: control word and
 // tickets zeroed on the handle's stream before the init, iterations in batches of cg_batch_iters with the
 // control word copied back per batch, a batch replayed as a graph captured from the handle's one stream (a
@@ -2110,7 +2004,7 @@ static mspmv_status bicgstab_solve_native(mspmv_handle_s *h, const double *d_b, 
 {
     if (h->m != h->n)
         return invalid("BiCGSTAB needs a square matrix");
-    if (ilu && (ilu->tri.n != h->m || ilu->tri.device != h->device))
+    if (ilu && (ilu->n != h->m || ilu->device != h->device))
         return invalid("the ILU(0) factor must match the matrix's shape and device");
     if (!supported_L(L))
         return (set_error("L must be one of 1, 2, 4, 8, 16"), MSPMV_ERR_UNSUPPORTED);
@@ -2146,9 +2040,9 @@ static mspmv_status bicgstab_solve_native(mspmv_handle_s *h, const double *d_b, 
         ST_TRY(ilu0_workspace(ilu, elems));
     const char *name = ilu ? "ILU0-BiCGSTAB" : "BiCGSTAB";
     h->last_cg_kernel = ilu ? "ILU0-BiCGSTAB (2 SpMM + 4 trsv + 5 passes)" : "BiCGSTAB (2 SpMM + 5 passes)";
-    if (ilu && ilu->tri.num_colors > 0)
+    if (ilu && ilu->num_colors > 0)
         h->last_cg_kernel =
-            "MC-ILU0-BiCGSTAB (2 SpMM + 4 sweeps of " + std::to_string(ilu->tri.num_colors) + " colours + 5 passes)";
+            "MC-ILU0-BiCGSTAB (2 SpMM + 4 sweeps of " + std::to_string(ilu->num_colors) + " colours + 5 passes)";
     h->last_solver_product = solver_product_kernel_name(h, *plan, splan, L);
     const int use_cap = hist ? cap : 0;
     const int saved_cap = h->hist_cap;
@@ -2173,12 +2067,9 @@ static mspmv_status bicgstab_solve_native(mspmv_handle_s *h, const double *d_b, 
             h->d_red, h->d_ctrl, h->d_hist, h->stream, plan, splan, tk,
             reinterpret_cast<const void *>((intptr_t)L), reinterpret_cast<const void *>((intptr_t)nblk),
             reinterpret_cast<const void *>((intptr_t)use_cap), reinterpret_cast<const void *>((intptr_t)K)};
-        if (ilu) {  // the factor, its generation, its value arrays, its workspace
-            key.insert(key.end(), {ilu, reinterpret_cast<const void *>((uintptr_t)ilu->tri.gen), ilu->tri.d_lva,
-                                   ilu->tri.d_uva, ilu->tri.d_y, ilu->d_hat});
-            if (ilu->tri.num_colors > 0)  // what the colour sweeps read besides: the ordering and the two patterns
-                key.insert(key.end(), {ilu->tri.d_perm, ilu->tri.d_lro, ilu->tri.d_lci, ilu->tri.d_uro, ilu->tri.d_uci,
-                                       reinterpret_cast<const void *>((intptr_t)ilu->tri.num_colors)});
+        if (ilu) {  // the factor and the hat panel
+            tri_graph_key(ilu, key);
+            key.push_back(ilu->d_hat);
             st = solver_graph(h, SolverGraph{h->pbicg_graph, h->pbicg_exec, h->pbicg_graph_key}, key, K, iterate, name);
             exec = h->pbicg_exec;
         } else {
@@ -2383,159 +2274,7 @@ mspmv_status mspmv_dpcg_spai_multi(mspmv_handle a, mspmv_handle m, const double 
     return cg_solve_host(a, B, X, L, max_iters, tolerance, iters, max_err_hist, hist_cap, m);
 }
 
-// ---- IC(0) factor on the device --------------------------------------------------------------
-// Two triangular CSRs on the device for the sync-free solves (launch_ic0_trsv): a lower one solved forward
-// (diagonal present in every row) and an upper one solved backward, with their level orders.  IC(0) passes L
-// and its transpose, ILU(0) passes L (unit diagonal stored) and U.
-// Level sets: a row's level is 1 + the deepest level among the rows it reads (L: columns
-// below the diagonal, solved ascending; L^T: columns above it, solved descending).  Waves
-// take rows in (level, row) order, so every awaited row is in an earlier level, hence an
-// earlier-dispatched wave, and a whole level's rows are solved concurrently (natural order
-// would chain every row to its left neighbour: ~15x slower on a 2-D stencil).
-static mspmv_status upload_triangles(int n, const int *lro, const int *lci, const double *lva, int lnnz,
-                                     const int *uro, const int *uci, const double *uva, int unnz, int device,
-                                     mspmv_ic0_s *m, const char *what)
-{
-    auto order_by_level = [&](const int *rp, const int *cp, bool fwd, std::vector<int> &order) {
-        std::vector<int> lev((size_t)n, 0);
-        int maxlev = 0;
-        for (int s = 0; s < n; ++s) {
-            const int i = fwd ? s : n - 1 - s;
-            int lv = 0;
-            for (int k = rp[i]; k < rp[i + 1]; ++k) {
-                const int j = cp[k];
-                if (fwd ? j < i : j > i)
-                    lv = std::max(lv, lev[j] + 1);
-            }
-            lev[i] = lv;
-            maxlev = std::max(maxlev, lv);
-        }
-        std::vector<int> cnt((size_t)maxlev + 2, 0);
-        for (int i = 0; i < n; ++i)
-            ++cnt[(size_t)lev[i] + 1];
-        for (int l2 = 0; l2 <= maxlev; ++l2)
-            cnt[(size_t)l2 + 1] += cnt[l2];
-        order.assign((size_t)std::max(n, 1), 0);
-        for (int s = 0; s < n; ++s) {
-            const int i = fwd ? s : n - 1 - s;
-            order[(size_t)cnt[lev[i]]++] = i;
-        }
-        return n ? maxlev + 1 : 0;
-    };
-    std::vector<int> fwd_order, bwd_order;
-    const int lf = order_by_level(lro, lci, true, fwd_order);
-    const int lb = order_by_level(uro, uci, false, bwd_order);
-    HIP_TRY(hipSetDevice(device));
-    m->levels_fwd = lf;
-    m->levels_bwd = lb;
-    m->device = device;
-    m->n = n;
-    m->nnz = lnnz;
-    mspmv_status st = MSPMV_OK;
-    auto up = [&](auto **d, const auto *src, size_t cnt) {
-        if (st != MSPMV_OK)
-            return;
-        st = dev_alloc(d, std::max<size_t>(cnt, 1));
-        if (st == MSPMV_OK && cnt && hipMemcpy(*d, src, sizeof(**d) * cnt, hipMemcpyHostToDevice) != hipSuccess) {
-            set_error(std::string(what) + " upload failed");
-            st = MSPMV_ERR_HIP;
-        }
-    };
-    up(&m->d_lro, lro, (size_t)n + 1);
-    up(&m->d_lci, lci, (size_t)lnnz);
-    up(&m->d_lva, lva, (size_t)lnnz);
-    up(&m->d_uro, uro, (size_t)n + 1);
-    up(&m->d_uci, uci, (size_t)unnz);
-    up(&m->d_uva, uva, (size_t)unnz);
-    up(&m->d_fwd_order, fwd_order.data(), (size_t)n);
-    up(&m->d_bwd_order, bwd_order.data(), (size_t)n);
-    return st;
-}
-
-mspmv_status mspmv_ic0_create(const mspmv_csr_d *l, int device, mspmv_ic0 *out)
-{
-    if (!out)
-        return invalid("null output");
-    *out = nullptr;
-    ST_TRY(validate_host_csr(l));
-    if (l->num_rows != l->num_cols)
-        return invalid("IC(0) factor must be square");
-    const int n = l->num_rows, nnz = l->num_nonzeros;
-    for (int r = 0; r < n; ++r)
-        if (l->row_offsets[r + 1] < l->row_offsets[r])
-            return invalid("row_offsets not monotone");
-    if (l->row_offsets[0] != 0 || l->row_offsets[n] != nnz)
-        return invalid("row_offsets inconsistent with num_nonzeros");
-    for (int k = 0; k < nnz; ++k)
-        if (l->column_indices[k] < 0 || l->column_indices[k] >= n)
-            return invalid("column index out of range");
-    // A lower-triangular factor with every diagonal present (IncompleteCholesky keeps A's lower
-    // pattern, diagonal included): an entry above the diagonal would make the forward solve wait
-    // on a row of a later level, a missing diagonal would divide by zero -- reject both here
-    // rather than stall on the GPU.
-    for (int r = 0; r < n; ++r) {
-        bool diag = false;
-        for (int k = l->row_offsets[r]; k < l->row_offsets[r + 1]; ++k) {
-            if (l->column_indices[k] > r)
-                return invalid("IC(0) factor has an entry above the diagonal in row " + std::to_string(r));
-            diag = diag || l->column_indices[k] == r;
-        }
-        if (!diag)
-            return invalid("IC(0) factor row " + std::to_string(r) + " has no diagonal entry");
-    }
-    // TransposeCsr (incomplete_cholesky_decomp.hpp:11-78): counting sort by column, rows in order
-    std::vector<int> uro((size_t)n + 1, 0), uci((size_t)std::max(nnz, 1));
-    std::vector<double> uva((size_t)std::max(nnz, 1));
-    for (int k = 0; k < nnz; ++k)
-        ++uro[(size_t)l->column_indices[k] + 1];
-    for (int c = 0; c < n; ++c)
-        uro[(size_t)c + 1] += uro[c];
-    {
-        std::vector<int> pos(uro.begin(), uro.end() - 1);
-        for (int r = 0; r < n; ++r)
-            for (int k = l->row_offsets[r]; k < l->row_offsets[r + 1]; ++k) {
-                const int d = pos[l->column_indices[k]]++;
-                uci[d] = r;
-                uva[d] = l->values[k];
-            }
-    }
-    mspmv_ic0_s *m = new mspmv_ic0_s;
-    const mspmv_status st = upload_triangles(n, l->row_offsets, l->column_indices, l->values, nnz, uro.data(),
-                                             uci.data(), uva.data(), nnz, device, m, "IC(0)");
-    if (st != MSPMV_OK) {
-        mspmv_ic0_destroy(m);
-        return st;
-    }
-    *out = m;
-    return MSPMV_OK;
-}
-
-// The device arrays of a factor's two triangles and its intermediate.
-static void ic0_release(mspmv_ic0_s *m)
-{
-    (void)hipSetDevice(m->device);
-    dev_free(m->d_lro);
-    dev_free(m->d_lci);
-    dev_free(m->d_lva);
-    dev_free(m->d_uro);
-    dev_free(m->d_uci);
-    dev_free(m->d_uva);
-    dev_free(m->d_fwd_order);
-    dev_free(m->d_bwd_order);
-    dev_free(m->d_perm);
-    if (m->d_y)
-        (void)hipFree(m->d_y);
-}
-
-mspmv_status mspmv_ic0_destroy(mspmv_ic0 m)
-{
-    if (!m)
-        return MSPMV_OK;
-    ic0_release(m);
-    delete m;
-    return MSPMV_OK;
-}
-
+// ---- IC(0)-preconditioned CG (the factor: mspmv_tri.hip) ---------------------------------------
 mspmv_status mspmv_dpcg_ic0_multi_dev(mspmv_handle a, mspmv_ic0 m, const double *d_B, double *d_X, int L,
                                       int max_iters, double tolerance, mspmv_spmm_kernel kernel, int *iters,
                                       double *max_err_hist, int hist_cap)
@@ -2555,253 +2294,6 @@ mspmv_status mspmv_dpcg_ic0_multi(mspmv_handle a, mspmv_ic0 m, const double *B, 
     if (!m)
         return invalid("null IC(0) factor");
     return cg_solve_host(a, B, X, L, max_iters, tolerance, iters, max_err_hist, hist_cap, nullptr, m);
-}
-
-// One triangular solve with a factor, alone: the pass the preconditioner applies run (launch_ic0_trsv), on a's
-// stream with a's control word, synchronised.  what: "IC(0)" / "ILU(0)"; which_msg: the selector's error text.
-static mspmv_status tri_solve_dev(mspmv_handle a, const mspmv_ic0_s *m, int which, const double *d_B, double *d_X,
-                                  int L, const char *what, const char *which_msg)
-{
-    ST_TRY(check_handle(a));
-    if (!m)
-        return invalid(std::string("null ") + what + " factor");
-    if (which != 0 && which != 1)
-        return invalid(which_msg);
-    if (a->m != a->n || m->n != a->m || m->device != a->device)
-        return invalid(std::string("the ") + what + " factor must match the matrix's shape and device");
-    if (!supported_L(L))
-        return (set_error("L must be one of 1, 2, 4, 8, 16"), MSPMV_ERR_UNSUPPORTED);
-    if (m->n == 0)
-        return MSPMV_OK;
-    if (!d_B || !d_X)
-        return invalid("null panel");
-    if (!aligned16(d_B) || !aligned16(d_X))
-        return invalid("triangular-solve panels must be 16-byte aligned");
-    const uintptr_t b0 = (uintptr_t)d_B, x0 = (uintptr_t)d_X, bytes = sizeof(double) * (size_t)m->n * L;
-    if (b0 < x0 + bytes && x0 < b0 + bytes)
-        return invalid("triangular-solve panels must not overlap (X is pre-filled with the pending pattern)");
-    if (!a->d_ctrl)
-        ST_TRY(dev_alloc(&a->d_ctrl, 1));
-    HIP_TRY(hipMemsetAsync(a->d_ctrl, 0, sizeof(CgControl), a->stream));
-    if (m->num_colors > 0)  // a multi-colour factor: one sweep per colour, in the colour ordering
-        HIP_TRY(launch_color_trsv(m, which != 0, d_B, d_X, L, a->d_ctrl, a->stream));
-    else
-        HIP_TRY(launch_ic0_trsv(m, which == 0, d_B, d_X, L, a->d_ctrl, a->stream));
-    HIP_TRY(hipStreamSynchronize(a->stream));
-    CgControl fin{};
-    HIP_TRY(hipMemcpy(&fin, a->d_ctrl, sizeof(CgControl), hipMemcpyDeviceToHost));
-    if (fin.breakdown == 2) {
-        set_error(std::string(what) + " solve: a triangular-solve dependency never became ready (solve stalled)");
-        return MSPMV_ERR_STALL;
-    }
-    return MSPMV_OK;
-}
-
-mspmv_status mspmv_ic0_solve_dev(mspmv_handle a, mspmv_ic0 m, int transpose, const double *d_B, double *d_X, int L)
-{
-    return tri_solve_dev(a, m, transpose, d_B, d_X, L, "IC(0)", "transpose must be 0 (L X = B) or 1 (L^T X = B)");
-}
-
-// ---- ILU(0) factor on the device --------------------------------------------------------------
-mspmv_status mspmv_ilu0_create(const mspmv_csr_d *lu, int device, mspmv_ilu0 *out)
-{
-    if (!out)
-        return invalid("null output");
-    *out = nullptr;
-    ST_TRY(ilu0_check_rows(lu, "ilu0_create"));
-    const int n = lu->num_rows, nnz = lu->num_nonzeros;
-    const int *ro = lu->row_offsets, *ci = lu->column_indices;
-    // L: the strictly lower entries, then a stored 1.0 diagonal (k_trsv_tagged finds a diagonal by j == i and
-    // divides by it: by 1.0, exactly); U: the diagonal first, then the upper entries.  A solve divides by U's
-    // diagonal: zero or non-finite is refused here.
-    std::vector<int> lro((size_t)n + 1, 0), uro((size_t)n + 1, 0);
-    std::vector<int> lci, uci;
-    std::vector<double> lva, uva;
-    lci.reserve((size_t)nnz + 1), lva.reserve((size_t)nnz + 1), uci.reserve((size_t)nnz + 1), uva.reserve((size_t)nnz + 1);
-    for (int i = 0; i < n; ++i) {
-        for (int k = ro[i]; k < ro[i + 1]; ++k) {
-            const double v = lu->values[k];
-            if (ci[k] < i) {
-                lci.push_back(ci[k]), lva.push_back(v);
-            } else {
-                if (ci[k] == i && (v == 0.0 || !std::isfinite(v)))
-                    return invalid("ILU(0) factor row " + std::to_string(i) + " has a zero or non-finite diagonal");
-                uci.push_back(ci[k]), uva.push_back(v);
-            }
-        }
-        lci.push_back(i), lva.push_back(1.0);
-        lro[(size_t)i + 1] = (int)lci.size();
-        uro[(size_t)i + 1] = (int)uci.size();
-    }
-    mspmv_ilu0_s *m = new mspmv_ilu0_s;
-    const mspmv_status st = upload_triangles(n, lro.data(), lci.data(), lva.data(), (int)lci.size(), uro.data(),
-                                             uci.data(), uva.data(), (int)uci.size(), device, &m->tri, "ILU(0)");
-    if (st != MSPMV_OK) {
-        mspmv_ilu0_destroy(m);
-        return st;
-    }
-    *out = m;
-    return MSPMV_OK;
-}
-
-mspmv_status mspmv_ilu0_destroy(mspmv_ilu0 m)
-{
-    if (!m)
-        return MSPMV_OK;
-    ic0_release(&m->tri);
-    dev_free(m->d_hat);
-    delete m;
-    return MSPMV_OK;
-}
-
-// The colours of a multi-colour factor whose triangles upload_triangles has placed in t: perm on the device, and per
-// colour the longest row of each triangle in off-diagonal entries (L's rows hold their diagonal when l_diag, U's
-// always), which picks a sweep's LONG instantiation.
-static mspmv_status upload_colors(mspmv_ic0_s *t, std::vector<int> &perm, std::vector<int> &color_off,
-                                  const std::vector<int> &lro, const std::vector<int> &uro, bool l_diag,
-                                  const char *what)
-{
-    const int n = t->n, C = (int)color_off.size() - 1;
-    ST_TRY(dev_alloc(&t->d_perm, (size_t)n));
-    if (n && hipMemcpy(t->d_perm, perm.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess) {
-        set_error(std::string(what) + " upload failed");
-        return MSPMV_ERR_HIP;
-    }
-    t->num_colors = C;
-    t->l_diag = l_diag;
-    t->lmax.assign((size_t)C, 0), t->umax.assign((size_t)C, 0);
-    for (int c = 0; c < C; ++c)
-        for (int i = color_off[c]; i < color_off[(size_t)c + 1]; ++i) {
-            t->lmax[c] = std::max(t->lmax[c], lro[(size_t)i + 1] - lro[i] - (l_diag ? 1 : 0));
-            t->umax[c] = std::max(t->umax[c], uro[(size_t)i + 1] - uro[i] - 1);
-        }
-    t->color_off.swap(color_off);
-    t->perm.swap(perm);
-    return MSPMV_OK;
-}
-
-mspmv_status mspmv_ilu0_create_colored(const mspmv_csr_d *a, const int *colors, int device, mspmv_ilu0 *out)
-{
-    if (!out)
-        return invalid("null output");
-    *out = nullptr;
-    // the checks, the ordering and the factorisation: all on the host, before the device is touched
-    std::vector<int> perm, color_off, lro, lci, uro, uci;
-    std::vector<double> lva, uva;
-    ST_TRY(ilu0_colored_host(a, colors, perm, color_off, lro, lci, lva, uro, uci, uva));
-    mspmv_ilu0_s *m = new mspmv_ilu0_s;
-    mspmv_status st = upload_triangles(a->num_rows, lro.data(), lci.data(), lva.data(), (int)lci.size(), uro.data(),
-                                       uci.data(), uva.data(), (int)uci.size(), device, &m->tri, "ILU(0)");
-    if (st == MSPMV_OK)
-        st = upload_colors(&m->tri, perm, color_off, lro, uro, false, "ILU(0)");
-    if (st != MSPMV_OK) {
-        mspmv_ilu0_destroy(m);
-        return st;
-    }
-    *out = m;
-    return MSPMV_OK;
-}
-
-static mspmv_status tri_colors(const mspmv_ic0_s *t, int *num_colors, int *perm, const char *who)
-{
-    if (!t || !num_colors)
-        return invalid(std::string(who) + ": null factor or output");
-    *num_colors = t->num_colors;
-    if (perm && t->num_colors > 0)
-        std::copy(t->perm.begin(), t->perm.end(), perm);
-    return MSPMV_OK;
-}
-
-mspmv_status mspmv_ilu0_colors(mspmv_ilu0 m, int *num_colors, int *perm)
-{
-    return tri_colors(m ? &m->tri : nullptr, num_colors, perm, "ilu0_colors");
-}
-
-mspmv_status mspmv_ilu0_solve_dev(mspmv_handle a, mspmv_ilu0 m, int upper, const double *d_B, double *d_X, int L)
-{
-    return tri_solve_dev(a, m ? &m->tri : nullptr, upper, d_B, d_X, L, "ILU(0)",
-                         "upper must be 0 (L X = B) or 1 (U X = B)");
-}
-
-// The preconditioner apply with a factor, alone: both triangles through the factor's intermediate, on a's stream
-// with a's control word, synchronised.  what: "IC(0)" / "ILU(0)".
-static mspmv_status tri_apply_dev(mspmv_handle a, mspmv_ic0_s *m, const double *d_B, double *d_X, int L,
-                                  const char *what)
-{
-    ST_TRY(check_handle(a));
-    if (!m)
-        return invalid(std::string("null ") + what + " factor");
-    if (a->m != a->n || m->n != a->m || m->device != a->device)
-        return invalid(std::string("the ") + what + " factor must match the matrix's shape and device");
-    if (!supported_L(L))
-        return (set_error("L must be one of 1, 2, 4, 8, 16"), MSPMV_ERR_UNSUPPORTED);
-    if (m->n == 0)
-        return MSPMV_OK;
-    if (!d_B || !d_X)
-        return invalid("null panel");
-    if (!aligned16(d_B) || !aligned16(d_X))
-        return invalid("preconditioner-apply panels must be 16-byte aligned");
-    const uintptr_t b0 = (uintptr_t)d_B, x0 = (uintptr_t)d_X, bytes = sizeof(double) * (size_t)m->n * L;
-    if (b0 < x0 + bytes && x0 < b0 + bytes)
-        return invalid("preconditioner-apply panels must not overlap");
-    ST_TRY(tri_workspace(m, (size_t)m->n * L, what));  // the intermediate d_y
-    HIP_TRY(hipSetDevice(a->device));
-    if (!a->d_ctrl)
-        ST_TRY(dev_alloc(&a->d_ctrl, 1));
-    HIP_TRY(hipMemsetAsync(a->d_ctrl, 0, sizeof(CgControl), a->stream));
-    if (m->num_colors > 0) {
-        HIP_TRY(launch_color_apply(m, d_B, d_X, L, a->d_ctrl, a->stream));
-    } else {
-        HIP_TRY(launch_ic0_trsv(m, true, d_B, m->d_y, L, a->d_ctrl, a->stream));
-        HIP_TRY(launch_ic0_trsv(m, false, m->d_y, d_X, L, a->d_ctrl, a->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(a->stream));
-    CgControl fin{};
-    HIP_TRY(hipMemcpy(&fin, a->d_ctrl, sizeof(CgControl), hipMemcpyDeviceToHost));
-    if (fin.breakdown == 2) {
-        set_error(std::string(what) + " apply: a triangular-solve dependency never became ready (solve stalled)");
-        return MSPMV_ERR_STALL;
-    }
-    return MSPMV_OK;
-}
-
-mspmv_status mspmv_ilu0_apply_dev(mspmv_handle a, mspmv_ilu0 m, const double *d_B, double *d_X, int L)
-{
-    return tri_apply_dev(a, m ? &m->tri : nullptr, d_B, d_X, L, "ILU(0)");
-}
-
-// ---- multi-colour IC(0) ----------------------------------------------------------------------
-mspmv_status mspmv_ic0_create_colored(const mspmv_csr_d *a, const int *colors, int device, double *shift,
-                                      mspmv_ic0 *out)
-{
-    if (!out)
-        return invalid("null output");
-    *out = nullptr;
-    // the checks, the ordering and the factorisation: all on the host, before the device is touched
-    std::vector<int> perm, color_off, lro, lci, uro, uci;
-    std::vector<double> lva, uva;
-    ST_TRY(ic0_colored_host(a, colors, perm, color_off, lro, lci, lva, uro, uci, uva, shift));
-    mspmv_ic0_s *m = new mspmv_ic0_s;
-    mspmv_status st = upload_triangles(a->num_rows, lro.data(), lci.data(), lva.data(), (int)lci.size(), uro.data(),
-                                       uci.data(), uva.data(), (int)uci.size(), device, m, "IC(0)");
-    if (st == MSPMV_OK)
-        st = upload_colors(m, perm, color_off, lro, uro, true, "IC(0)");
-    if (st != MSPMV_OK) {
-        mspmv_ic0_destroy(m);
-        return st;
-    }
-    *out = m;
-    return MSPMV_OK;
-}
-
-mspmv_status mspmv_ic0_colors(mspmv_ic0 m, int *num_colors, int *perm)
-{
-    return tri_colors(m, num_colors, perm, "ic0_colors");
-}
-
-mspmv_status mspmv_ic0_apply_dev(mspmv_handle a, mspmv_ic0 m, const double *d_B, double *d_X, int L)
-{
-    return tri_apply_dev(a, m, d_B, d_X, L, "IC(0)");
 }
 
 // ---- measurement ---------------------------------------------------------------------------

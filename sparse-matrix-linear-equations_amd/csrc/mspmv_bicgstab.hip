@@ -14,7 +14,7 @@
 // Right-preconditioned with an ILU(0) factor M = L U (mspmv_dpbicgstab_ilu0_multi; launch_pbicgstab_iteration):
 //     Phat = U^-1 L^-1 P;  V = A Phat;  ...  X += alpha Phat;  Shat = U^-1 L^-1 s;  T = A Shat;  ...  X += omega Shat
 // and everything else as above: R is the original system's residual, so the stop test and the history mean the
-// same.  Four sync-free triangular solves per iteration (launch_ic0_trsv: L into the factor's intermediate, U
+// same.  Two applies of the factor per iteration (tri_apply, mspmv_tri.hip: L into the factor's intermediate, U
 // into the factor's hat panel, which Phat and then Shat share), and the s and update passes in their PRE
 // instantiation, which take X's direction from the hat panel; the other three passes are shared.
 // Compiled with -ffp-contract=off like every kernel here: every a*b+c is two roundings.
@@ -463,24 +463,12 @@ hipError_t launch_bicgstab_iteration(mspmv_handle_s *h, const TilePlan &plan, co
     });
 }
 
-// dst = U^-1 L^-1 src through the factor's intermediate; every solve's output is a panel of its own (the
-// pending-pattern fill overwrites it first).
-static hipError_t ilu0_apply(mspmv_handle_s *h, mspmv_ilu0_s *ilu, int L, const double *src, double *dst)
-{
-    if (ilu->tri.num_colors > 0)  // a multi-colour factor: 2 C colour sweeps, no fill (mspmv_color.hip)
-        return launch_color_apply(&ilu->tri, src, dst, L, h->d_ctrl, h->stream);
-    hipError_t e = launch_ic0_trsv(&ilu->tri, true, src, ilu->tri.d_y, L, h->d_ctrl, h->stream);
-    if (e == hipSuccess)
-        e = launch_ic0_trsv(&ilu->tri, false, ilu->tri.d_y, dst, L, h->d_ctrl, h->stream);
-    return e;
-}
-
 hipError_t launch_pbicgstab_iteration(mspmv_handle_s *h, mspmv_ilu0_s *ilu, const TilePlan &plan,
                                       const TilePlan *splan, double *d_x, int L, int nblk, double tol)
 {
     BicgArgs a = bicg_args(h, d_x, L, tol);
     a.hat = ilu->d_hat;
-    hipError_t e = ilu0_apply(h, ilu, L, h->d_p0, ilu->d_hat);  // Phat
+    hipError_t e = tri_apply(ilu, h->d_p0, ilu->d_hat, L, h->d_ctrl, h->stream);  // Phat
     if (e != hipSuccess)
         return e;
     if ((e = launch_solver_product(h, plan, splan, ilu->d_hat, h->d_ap, L)) != hipSuccess)  // V = A Phat
@@ -493,7 +481,7 @@ hipError_t launch_pbicgstab_iteration(mspmv_handle_s *h, mspmv_ilu0_s *ilu, cons
         hipError_t el = hipGetLastError();
         if (el != hipSuccess)
             return el;
-        if ((el = ilu0_apply(h, ilu, L, h->d_r, ilu->d_hat)) != hipSuccess)  // Shat (Phat is dead)
+        if ((el = tri_apply(ilu, h->d_r, ilu->d_hat, L, h->d_ctrl, h->stream)) != hipSuccess)  // Shat (Phat is dead)
             return el;
         if ((el = launch_solver_product(h, plan, splan, ilu->d_hat, h->d_p1, L)) != hipSuccess)  // T = A Shat
             return el;

@@ -1,8 +1,8 @@
 // mspmv_cg_passes.hip -- the CG layer above the products: the streaming vector passes of the split
 // (multi-RHS) iteration, the pipelined single-RHS CG's passes, the row-sharded CG's passes, the
-// sync-free triangular solves of the IC(0) apply, the k_fold_dot reduction, and the per-iteration
-// launchers of plain, split, SPAI and IC(0) CG.  The products themselves live in mspmv_kernels.hip
-// (merge-path tiles), mspmv_dia.hip (offset windows) and mspmv_slab.hip (column slabs); this file
+// k_fold_dot reduction, and the per-iteration launchers of plain, split, SPAI and IC(0) CG.  The
+// products themselves live in mspmv_kernels.hip (merge-path tiles), mspmv_dia.hip (offset windows)
+// and mspmv_slab.hip (column slabs), the IC(0) apply in mspmv_tri.hip (tri_apply); this file
 // reaches them through the launchers declared in mspmv_internal.h only.
 // Compiled with -ffp-contract=off like every kernel here: every a*b+c is two roundings.
 #include "mspmv_internal.h"
@@ -374,81 +374,6 @@ __global__ __launch_bounds__(kBlock) void k_cg_xflush(CgVecArgs a, const double 
     const long long stride = (long long)gridDim.x * kBlock;
     for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < a.n_elems; i += stride)
         a.x[i] = a.x[i] + a.scal[L == 1 ? 0 : (int)(i % L)].alpha * p[i];
-}
-
-// ---- IC(0) preconditioner apply: sync-free sparse triangular solves ---------------------------
-// x = T^-1 b for a triangular CSR T, one wave per row: ForwardSolveMultiple (FWD, T = L lower, rows
-// ascending) and BackwardSolveMultiple (T = L^T upper, rows descending),
-// incomplete_cholesky_decomp.hpp:231-348.  Waves are dispatched in dependency-level order and wait
-// only on rows of earlier levels, so every awaited row belongs to a wave already resident or
-// finished: no deadlock.  Data-tagged values: the output starts filled with a NaN pattern no
-// arithmetic produces (kTrsvPending, written by one 32-bit fill), a row's x values are stored by
-// single 8-B write-through stores, and a consumer lane polls the very value it needs until the
-// pattern is gone -- one memory round trip per dependency hop (ready flags: poll, load, store, drain,
-// raise -- measured 9.8 vs 6.35 ms per iteration, round 1).  Bounded: after ~2^20 polls the solve
-// reports a stall instead of hanging the GPU.  The partial sums are folded in a tree, not in CSR
-// order (the reference's sequential sum): results agree to rounding.
-constexpr unsigned kTrsvPendingWord = 0x7ff4deadu;
-constexpr unsigned long long kTrsvPending = 0x7ff4dead7ff4deadull;
-
-__device__ __forceinline__ bool wait_value(const double *p, double &out)
-{
-    for (int it = 0; it < (1 << 20); ++it) {
-        const double v = load_sc1(p);
-        if ((unsigned long long)__double_as_longlong(v) != kTrsvPending) {
-            out = v;
-            return true;
-        }
-        __builtin_amdgcn_s_sleep(1);
-    }
-    out = 0.0;
-    return false;
-}
-
-template <int L, bool FWD>
-__global__ __launch_bounds__(kBlock) void k_trsv_tagged(const int *__restrict__ ro, const int *__restrict__ ci,
-                                                        const double *__restrict__ va, int n,
-                                                        const int *__restrict__ order, const double *b, double *x,
-                                                        CgControl *ctrl)
-{
-    constexpr int NZ = 64 / L;
-    const int w = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
-    if (w >= n || ctrl->done)  // done is set only by earlier launches: uniform here
-        return;
-    const int i = order[w];  // rows in (level, row) order: awaited rows belong to earlier waves
-    const int lane = threadIdx.x & 63;
-    const int v = lane % L, q = lane / L;
-    const int k1 = ro[i + 1];
-    double sum = 0.0, diag = 0.0;
-    bool ok = true;
-    for (int k0 = ro[i]; k0 < k1; k0 += NZ) {
-        const int k = k0 + q;
-        if (k < k1) {
-            const int j = ci[k];
-            const double a = va[k];
-            if (j == i) {
-                diag = a;
-            } else {
-                double xj;
-                ok = wait_value(&x[(size_t)j * L + v], xj) && ok;
-                sum += a * xj;
-            }
-        }
-    }
-#pragma unroll
-    for (int off = L; off < 64; off <<= 1) {
-        sum += __shfl_xor(sum, off);
-        diag += __shfl_xor(diag, off);
-    }
-    if (q == 0) {
-        const double bi = b[(size_t)i * L + v];
-        const double xi = (!FWD && diag == 0.0) ? 0.0 : (bi - sum) / diag;
-        store_sc1(&x[(size_t)i * L + v], xi);
-    }
-    if (__ballot(!ok) != 0 && lane == 0) {  // a dependency never arrived: MSPMV_ERR_STALL, never hung
-        ctrl->breakdown = 2;
-        __hip_atomic_store(&ctrl->done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
 }
 
 // R.Z per column and the PCG scalars after it (PCGSolveMultiple): mode 0 (init, :96-104)
@@ -1080,46 +1005,8 @@ hipError_t launch_pcg_iteration(mspmv_handle_s *h, mspmv_handle_s *hm, const Til
     return launch_dist_vec(CgVecPass::PUpdate, va, L, nblk, h->d_p0, h->stream);
 }
 // ---- IC(0)-preconditioned block CG (PCGSolveMultiple) -------------------------------------------
-template <int L>
-static void trsv_L(const mspmv_ic0_s *ic, bool fwd, const double *b, double *x, CgControl *ctrl, hipStream_t s)
-{
-    const dim3 grid((ic->n + kBlock / 64 - 1) / (kBlock / 64)), block(kBlock);
-    if (fwd)
-        hipLaunchKernelGGL((k_trsv_tagged<L, true>), grid, block, 0, s, ic->d_lro, ic->d_lci, ic->d_lva, ic->n,
-                           ic->d_fwd_order, b, x, ctrl);
-    else
-        hipLaunchKernelGGL((k_trsv_tagged<L, false>), grid, block, 0, s, ic->d_uro, ic->d_uci, ic->d_uva, ic->n,
-                           ic->d_bwd_order, b, x, ctrl);
-}
-
-// One pass: the output panel filled with the pending pattern (one 32-bit fill), then the solve.
-hipError_t launch_ic0_trsv(const mspmv_ic0_s *ic, bool fwd, const double *d_b, double *d_x, int L, CgControl *ctrl,
-                           hipStream_t s)
-{
-    if (ic->n == 0)
-        return hipSuccess;
-    hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_x), kTrsvPendingWord, 2 * (size_t)ic->n * L, s);
-    if (e != hipSuccess)
-        return e;
-    return dispatch_L(L, [&](auto Lc) {
-        trsv_L<decltype(Lc)::value>(ic, fwd, d_b, d_x, ctrl, s);
-        return hipGetLastError();
-    });
-}
-
-// Z = L^-T (L^-1 R): ForwardSolveMultiple into ic->d_y, then BackwardSolveMultiple
-// (incomplete_cholesky.hpp:89-92, :166-167), each into a panel pre-filled with the pending pattern.  A multi-colour
-// factor: 2 C - 1 colour sweeps through ic->d_y, no fill (mspmv_color.hip).
-static hipError_t ic0_apply(mspmv_handle_s *h, mspmv_ic0_s *ic, int L, const double *r, double *z)
-{
-    if (ic->num_colors > 0)
-        return launch_color_apply(ic, r, z, L, h->d_ctrl, h->stream);
-    hipError_t e = launch_ic0_trsv(ic, true, r, ic->d_y, L, h->d_ctrl, h->stream);
-    if (e == hipSuccess)
-        e = launch_ic0_trsv(ic, false, ic->d_y, z, L, h->d_ctrl, h->stream);
-    return e;
-}
-
+// Z = M^-1 R is tri_apply (mspmv_tri.hip): L^-T (L^-1 R), ForwardSolveMultiple then BackwardSolveMultiple
+// (incomplete_cholesky.hpp:89-92, :166-167), through ic->d_y.
 // X = 0, R = B, b_norms (incomplete_cholesky.hpp:66-85); Z = M^-1 R (:87-92); P = Z (:94-95);
 // rs_old = R.Z (:97).  Z lives in h->d_p1, P in h->d_p0.
 hipError_t launch_pcg_ic0_init(mspmv_handle_s *h, mspmv_ic0_s *ic, const double *d_b, double *d_x, int L, double tol,
@@ -1127,7 +1014,7 @@ hipError_t launch_pcg_ic0_init(mspmv_handle_s *h, mspmv_ic0_s *ic, const double 
 {
     hipError_t e = launch_cg_init(h, d_b, d_x, L, tol, nblk);
     if (e == hipSuccess)
-        e = ic0_apply(h, ic, L, h->d_r, h->d_p1);
+        e = tri_apply(ic, h->d_r, h->d_p1, L, h->d_ctrl, h->stream);
     CgVecArgs va = pcg_vec_args(h, d_x, L, tol);
     va.p = h->d_p1;
     if (e == hipSuccess)
@@ -1150,7 +1037,7 @@ hipError_t launch_pcg_ic0_iteration(mspmv_handle_s *h, mspmv_ic0_s *ic, const Ti
     if (e == hipSuccess)
         e = launch_dist_vec(CgVecPass::XrUpdate, va, L, nblk, nullptr, h->stream);
     if (e == hipSuccess)
-        e = ic0_apply(h, ic, L, h->d_r, h->d_p1);
+        e = tri_apply(ic, h->d_r, h->d_p1, L, h->d_ctrl, h->stream);
     CgVecArgs vd = va;
     vd.p = h->d_p1;
     if (e == hipSuccess)

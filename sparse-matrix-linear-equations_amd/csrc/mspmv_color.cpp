@@ -11,31 +11,13 @@
 //   * ic0_colored_host: the same colours, perm and Ap (color_order, shared) -> mspmv_ic0_factor of Ap, diagonal
 //     shifts included -> L (diagonal last) and L^T by mspmv_csr_transpose (diagonal first).
 // Everything here runs before the device is touched.
-#include "mspmv.h"
+#include "mspmv_host.h"
 
 #include <algorithm>
-#include <string>
 #include <utility>
-#include <vector>
 
-namespace mspmv {
-void set_error(const std::string &msg);
-mspmv_status ilu0_check_rows(const mspmv_csr_d *a, const char *who);
-mspmv_status ilu0_colored_host(const mspmv_csr_d *a, const int *colors, std::vector<int> &perm,
-                               std::vector<int> &color_off, std::vector<int> &lro, std::vector<int> &lci,
-                               std::vector<double> &lva, std::vector<int> &uro, std::vector<int> &uci,
-                               std::vector<double> &uva);
-mspmv_status ic0_colored_host(const mspmv_csr_d *a, const int *colors, std::vector<int> &perm,
-                              std::vector<int> &color_off, std::vector<int> &lro, std::vector<int> &lci,
-                              std::vector<double> &lva, std::vector<int> &uro, std::vector<int> &uci,
-                              std::vector<double> &uva, double *shift);
-}
-
-static mspmv_status invalid(const std::string &msg)
-{
-    mspmv::set_error(msg);
-    return MSPMV_ERR_INVALID;
-}
+using mspmv::HostFactor;
+using mspmv::invalid;
 
 // colors[i] for a matrix that passed ilu0_check_rows; returns the number of colours
 static int greedy(const mspmv_csr_d *a, int *colors)
@@ -122,24 +104,16 @@ extern "C" MSPMV_API mspmv_status mspmv_csr_permute_sym(const mspmv_csr_d *a, co
                                                         double *va)
 {
     const char *who = "csr_permute_sym";
-    if (!a || a->num_rows < 0 || a->num_nonzeros < 0 || !a->row_offsets ||
-        (a->num_nonzeros > 0 && (!a->column_indices || !a->values)))
-        return invalid(std::string(who) + ": bad arguments");
+    mspmv_status st = mspmv::check_csr(a, who);
+    if (st != MSPMV_OK)
+        return st;
     if (a->num_rows != a->num_cols)
         return invalid(std::string(who) + ": a symmetric permutation needs a square matrix");
     const int n = a->num_rows;
     if (!ro || (n > 0 && !perm) || (a->num_nonzeros > 0 && (!ci || !va)))
         return invalid(std::string(who) + ": null permutation or output");
-    if (a->row_offsets[0] != 0 || a->row_offsets[n] != a->num_nonzeros)
-        return invalid(std::string(who) + ": row_offsets inconsistent with num_nonzeros");
-    for (int r = 0; r < n; ++r)
-        if (a->row_offsets[r + 1] < a->row_offsets[r])
-            return invalid(std::string(who) + ": row_offsets not monotone");
-    for (int k = 0; k < a->num_nonzeros; ++k)
-        if (a->column_indices[k] < 0 || a->column_indices[k] >= n)
-            return invalid(std::string(who) + ": column index out of range");
     std::vector<int> inv;
-    mspmv_status st = inverse_perm(n, perm, inv, who);
+    st = inverse_perm(n, perm, inv, who);
     if (st != MSPMV_OK)
         return st;
     permute(a, perm, inv, ro, ci, va);
@@ -204,19 +178,15 @@ static mspmv_status color_order(const mspmv_csr_d *a, const int *colors, const c
     return MSPMV_OK;
 }
 
-mspmv_status mspmv::ilu0_colored_host(const mspmv_csr_d *a, const int *colors, std::vector<int> &perm,
-                                      std::vector<int> &color_off, std::vector<int> &lro, std::vector<int> &lci,
-                                      std::vector<double> &lva, std::vector<int> &uro, std::vector<int> &uci,
-                                      std::vector<double> &uva)
+mspmv_status mspmv::ilu0_colored_host(const mspmv_csr_d *a, const int *colors, HostFactor &f)
 {
     const char *who = "ilu0_create_colored";
     mspmv_status st = ilu0_check_rows(a, who);
     if (st != MSPMV_OK)
         return st;
-    const int n = a->num_rows, nnz = a->num_nonzeros;
     std::vector<int> pro, pci;
-    std::vector<double> pva, lu((size_t)std::max(nnz, 1));
-    st = color_order(a, colors, who, perm, color_off, pro, pci, pva);
+    std::vector<double> pva, lu((size_t)std::max(a->num_nonzeros, 1));
+    st = color_order(a, colors, who, f.perm, f.color_off, pro, pci, pva);
     if (st != MSPMV_OK)
         return st;
     mspmv_csr_d ap = *a;
@@ -228,28 +198,13 @@ mspmv_status mspmv::ilu0_colored_host(const mspmv_csr_d *a, const int *colors, s
         set_error(std::string(mspmv_last_error()) + " [ilu0_create_colored: rows numbered in the colour ordering]");
         return st;
     }
-    lro.assign((size_t)n + 1, 0), uro.assign((size_t)n + 1, 0);
-    lci.clear(), lva.clear(), uci.clear(), uva.clear();
-    lci.reserve((size_t)nnz), lva.reserve((size_t)nnz), uci.reserve((size_t)nnz), uva.reserve((size_t)nnz);
-    for (int i = 0; i < n; ++i) {
-        for (int k = pro[i]; k < pro[i + 1]; ++k) {
-            if (pci[k] < i)
-                lci.push_back(pci[k]), lva.push_back(lu[k]);
-            else  // the diagonal first: the columns ascend
-                uci.push_back(pci[k]), uva.push_back(lu[k]);
-        }
-        lro[(size_t)i + 1] = (int)lci.size();
-        uro[(size_t)i + 1] = (int)uci.size();
-    }
+    split_lu(a->num_rows, pro.data(), pci.data(), lu.data(), false, f);
     return MSPMV_OK;
 }
 
 // A's structure by mspmv_ic0_nnz's checks (square, consistent offsets, columns in range: all the colouring and the
 // permutation need); the rows by mspmv_ic0_factor's own, on the permuted matrix, with its diagonal-shift retries.
-mspmv_status mspmv::ic0_colored_host(const mspmv_csr_d *a, const int *colors, std::vector<int> &perm,
-                                     std::vector<int> &color_off, std::vector<int> &lro, std::vector<int> &lci,
-                                     std::vector<double> &lva, std::vector<int> &uro, std::vector<int> &uci,
-                                     std::vector<double> &uva, double *shift)
+mspmv_status mspmv::ic0_colored_host(const mspmv_csr_d *a, const int *colors, HostFactor &f, double *shift)
 {
     const char *who = "ic0_create_colored";
     int lnnz = 0;
@@ -259,7 +214,7 @@ mspmv_status mspmv::ic0_colored_host(const mspmv_csr_d *a, const int *colors, st
     const int n = a->num_rows;
     std::vector<int> pro, pci;
     std::vector<double> pva;
-    st = color_order(a, colors, who, perm, color_off, pro, pci, pva);
+    st = color_order(a, colors, who, f.perm, f.color_off, pro, pci, pva);
     if (st != MSPMV_OK)
         return st;
     mspmv_csr_d ap = *a;
@@ -269,20 +224,20 @@ mspmv_status mspmv::ic0_colored_host(const mspmv_csr_d *a, const int *colors, st
     st = mspmv_ic0_nnz(&ap, &lnnz);
     if (st != MSPMV_OK)
         return st;
-    lro.assign((size_t)n + 1, 0), uro.assign((size_t)n + 1, 0);
-    lci.assign((size_t)std::max(lnnz, 1), 0), uci.assign((size_t)std::max(lnnz, 1), 0);
-    lva.assign((size_t)std::max(lnnz, 1), 0.0), uva.assign((size_t)std::max(lnnz, 1), 0.0);
-    st = mspmv_ic0_factor(&ap, lro.data(), lci.data(), lva.data(), shift);
+    f.lro.assign((size_t)n + 1, 0), f.uro.assign((size_t)n + 1, 0);
+    f.lci.assign((size_t)std::max(lnnz, 1), 0), f.uci.assign((size_t)std::max(lnnz, 1), 0);
+    f.lva.assign((size_t)std::max(lnnz, 1), 0.0), f.uva.assign((size_t)std::max(lnnz, 1), 0.0);
+    st = mspmv_ic0_factor(&ap, f.lro.data(), f.lci.data(), f.lva.data(), shift);
     if (st != MSPMV_OK) {
         set_error(std::string(mspmv_last_error()) + " [ic0_create_colored: rows numbered in the colour ordering]");
         return st;
     }
     mspmv_csr_d l = ap;
     l.num_nonzeros = lnnz;
-    l.row_offsets = lro.data();
-    l.column_indices = lci.data();
-    l.values = lva.data();
-    st = mspmv_csr_transpose(&l, uro.data(), uci.data(), uva.data());
-    lci.resize((size_t)lnnz), lva.resize((size_t)lnnz), uci.resize((size_t)lnnz), uva.resize((size_t)lnnz);
+    l.row_offsets = f.lro.data();
+    l.column_indices = f.lci.data();
+    l.values = f.lva.data();
+    st = mspmv_csr_transpose(&l, f.uro.data(), f.uci.data(), f.uva.data());
+    f.lci.resize((size_t)lnnz), f.lva.resize((size_t)lnnz), f.uci.resize((size_t)lnnz), f.uva.resize((size_t)lnnz);
     return st;
 }

@@ -180,7 +180,7 @@ __global__ __launch_bounds__(kBlock) void k_trsv_color(const int *__restrict__ r
 
 // One colour's launch.
 template <int L, TriForm T, bool PERM>
-static void color_sweep(const mspmv_ic0_s *t, int c, const double *b, double *x, double *out, const CgControl *ctrl,
+static void color_sweep(const TriFactor *t, int c, const double *b, double *x, double *out, const CgControl *ctrl,
                         hipStream_t s)
 {
     constexpr int GL = L > 1 ? L / 2 : 1;
@@ -196,7 +196,7 @@ static void color_sweep(const mspmv_ic0_s *t, int c, const double *b, double *x,
     });
 }
 
-hipError_t launch_color_trsv(const mspmv_ic0_s *t, bool upper, const double *d_b, double *d_x, int L,
+hipError_t launch_color_trsv(const TriFactor *t, bool upper, const double *d_b, double *d_x, int L,
                              const CgControl *ctrl, hipStream_t s)
 {
     const int C = t->num_colors;
@@ -214,7 +214,7 @@ hipError_t launch_color_trsv(const mspmv_ic0_s *t, bool upper, const double *d_b
     });
 }
 
-hipError_t launch_color_apply(const mspmv_ic0_s *t, const double *d_src, double *d_dst, int L, const CgControl *ctrl,
+hipError_t launch_color_apply(const TriFactor *t, const double *d_src, double *d_dst, int L, const CgControl *ctrl,
                               hipStream_t s)
 {
     const int C = t->num_colors;

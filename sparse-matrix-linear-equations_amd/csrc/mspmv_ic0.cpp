@@ -9,59 +9,31 @@
 //     1e-3, then x10 per attempt, 20 attempts (:150-173, :213-225).
 // The reference factorizes sequentially on the CPU; this is setup, run once, and stays on the
 // host the same way.  The two triangular solves it feeds run on the GPU every iteration
-// (k_trsv_tagged, sync-free, mspmv_cg_passes.hip).
-#include "mspmv.h"
+// (k_trsv_tagged, sync-free, mspmv_tri.hip).
+#include "mspmv_host.h"
 
 #include <cmath>
-#include <string>
-#include <vector>
 
-namespace mspmv {
-void set_error(const std::string &msg);
-}
+using mspmv::invalid;
 
-namespace {
-
-mspmv_status check_square(const mspmv_csr_d *a)
+// mspmv_ic0_nnz's and mspmv_ic0_factor's matrix: a consistent CSR, square.
+static mspmv_status check_square(const mspmv_csr_d *a)
 {
-    if (!a || a->num_rows < 0 || a->num_nonzeros < 0 || !a->row_offsets ||
-        (a->num_nonzeros > 0 && (!a->column_indices || !a->values))) {
-        mspmv::set_error("ic0: bad arguments");
-        return MSPMV_ERR_INVALID;
-    }
-    if (a->num_rows != a->num_cols) {
-        mspmv::set_error("ic0: IC(0) needs a square (symmetric) matrix");
-        return MSPMV_ERR_INVALID;
-    }
-    const int n = a->num_rows;
-    if (a->row_offsets[0] != 0 || a->row_offsets[n] != a->num_nonzeros) {
-        mspmv::set_error("ic0: row_offsets inconsistent with num_nonzeros");
-        return MSPMV_ERR_INVALID;
-    }
-    for (int r = 0; r < n; ++r)
-        if (a->row_offsets[r + 1] < a->row_offsets[r]) {
-            mspmv::set_error("ic0: row_offsets not monotone");
-            return MSPMV_ERR_INVALID;
-        }
-    for (int i = 0; i < a->num_nonzeros; ++i)
-        if (a->column_indices[i] < 0 || a->column_indices[i] >= n) {
-            mspmv::set_error("ic0: column index out of range");
-            return MSPMV_ERR_INVALID;
-        }
+    mspmv_status st = mspmv::check_csr(a, "ic0");
+    if (st != MSPMV_OK)
+        return st;
+    if (a->num_rows != a->num_cols)
+        return invalid("ic0: IC(0) needs a square (symmetric) matrix");
     return MSPMV_OK;
 }
-
-}  // namespace
 
 extern "C" MSPMV_API mspmv_status mspmv_ic0_nnz(const mspmv_csr_d *a, int *nnz_l)
 {
     mspmv_status st = check_square(a);
     if (st != MSPMV_OK)
         return st;
-    if (!nnz_l) {
-        mspmv::set_error("ic0: null output");
-        return MSPMV_ERR_INVALID;
-    }
+    if (!nnz_l)
+        return invalid("ic0: null output");
     int c = 0;
     for (int i = 0; i < a->num_rows; ++i)
         for (int k = a->row_offsets[i]; k < a->row_offsets[i + 1]; ++k)
@@ -76,10 +48,8 @@ extern "C" MSPMV_API mspmv_status mspmv_ic0_factor(const mspmv_csr_d *a, int *l_
     mspmv_status st = check_square(a);
     if (st != MSPMV_OK)
         return st;
-    if (!l_row_offsets || (a->num_nonzeros > 0 && (!l_cols || !l_vals))) {
-        mspmv::set_error("ic0: null output");
-        return MSPMV_ERR_INVALID;
-    }
+    if (!l_row_offsets || (a->num_nonzeros > 0 && (!l_cols || !l_vals)))
+        return invalid("ic0: null output");
     const int n = a->num_rows;
     const int *ro = a->row_offsets, *ci = a->column_indices;
     // The merge walk below and "row k's last entry is its diagonal" hold only when each row's
@@ -89,17 +59,13 @@ extern "C" MSPMV_API mspmv_status mspmv_ic0_factor(const mspmv_csr_d *a, int *l_
         int prev = -1;
         for (int k = ro[i]; k < ro[i + 1]; ++k)
             if (ci[k] <= i) {
-                if (ci[k] <= prev) {
-                    mspmv::set_error("ic0: row " + std::to_string(i) +
-                                     ": the entries with column <= row must be strictly ascending");
-                    return MSPMV_ERR_INVALID;
-                }
+                if (ci[k] <= prev)
+                    return invalid("ic0: row " + std::to_string(i) +
+                                   ": the entries with column <= row must be strictly ascending");
                 prev = ci[k];
             }
-        if (prev != i) {
-            mspmv::set_error("ic0: row " + std::to_string(i) + " has no diagonal entry");
-            return MSPMV_ERR_INVALID;
-        }
+        if (prev != i)
+            return invalid("ic0: row " + std::to_string(i) + " has no diagonal entry");
     }
     l_row_offsets[0] = 0;
     int nz = 0;
@@ -170,21 +136,12 @@ extern "C" MSPMV_API mspmv_status mspmv_ic0_factor(const mspmv_csr_d *a, int *l_
 extern "C" MSPMV_API mspmv_status mspmv_csr_transpose(const mspmv_csr_d *in, int *out_row_offsets, int *out_cols,
                                                       double *out_vals)
 {
-    if (!in || in->num_rows < 0 || in->num_cols < 0 || in->num_nonzeros < 0 || !in->row_offsets ||
-        !out_row_offsets || (in->num_nonzeros > 0 && (!in->column_indices || !in->values || !out_cols || !out_vals))) {
-        mspmv::set_error("csr_transpose: bad arguments");
-        return MSPMV_ERR_INVALID;
-    }
+    mspmv_status st = mspmv::check_csr(in, "csr_transpose");
+    if (st != MSPMV_OK)
+        return st;
+    if (!out_row_offsets || (in->num_nonzeros > 0 && (!out_cols || !out_vals)))
+        return invalid("csr_transpose: bad arguments");
     const int m = in->num_rows, n = in->num_cols, nnz = in->num_nonzeros;
-    if (in->row_offsets[0] != 0 || in->row_offsets[m] != nnz) {
-        mspmv::set_error("csr_transpose: row_offsets inconsistent with num_nonzeros");
-        return MSPMV_ERR_INVALID;
-    }
-    for (int k = 0; k < nnz; ++k)
-        if (in->column_indices[k] < 0 || in->column_indices[k] >= n) {
-            mspmv::set_error("csr_transpose: column index out of range");
-            return MSPMV_ERR_INVALID;
-        }
     std::vector<int> pos((size_t)n + 1, 0);
     for (int k = 0; k < nnz; ++k)
         ++pos[(size_t)in->column_indices[k] + 1];

@@ -10,63 +10,36 @@
 //     shifting.
 // Sequential host code, like mspmv_ic0_factor: setup, run once.  Compiled with -ffp-contract=off:
 // every l * u and the subtraction after it round separately.  The four triangular solves it feeds run
-// on the GPU every iteration (k_trsv_tagged, mspmv_cg_passes.hip).
-#include "mspmv.h"
+// on the GPU every iteration (k_trsv_tagged, mspmv_tri.hip).
+#include "mspmv_host.h"
 
 #include <cmath>
-#include <string>
-#include <vector>
 
-namespace mspmv {
-void set_error(const std::string &msg);
-mspmv_status ilu0_check_rows(const mspmv_csr_d *a, const char *who);
-}
+using mspmv::invalid;
 
 // Square, consistent offsets, columns in range; every row's columns strictly ascending (sorted, no
 // duplicates) and holding the diagonal.  MSPMV_ERR_INVALID, the message naming the first offending
-// row.  Shared by mspmv_ilu0_values and mspmv_ilu0_create (mspmv_api.hip).
+// row.  Shared by mspmv_ilu0_values, mspmv_color_greedy and the device factors' create calls (mspmv_tri.hip).
 mspmv_status mspmv::ilu0_check_rows(const mspmv_csr_d *a, const char *who)
 {
     const std::string w = std::string(who) + ": ";
-    if (!a || a->num_rows < 0 || a->num_nonzeros < 0 || !a->row_offsets ||
-        (a->num_nonzeros > 0 && (!a->column_indices || !a->values))) {
-        set_error(w + "bad arguments");
-        return MSPMV_ERR_INVALID;
-    }
-    if (a->num_rows != a->num_cols) {
-        set_error(w + "ILU(0) needs a square matrix");
-        return MSPMV_ERR_INVALID;
-    }
+    mspmv_status st = check_csr(a, who);
+    if (st != MSPMV_OK)
+        return st;
+    if (a->num_rows != a->num_cols)
+        return invalid(w + "ILU(0) needs a square matrix");
     const int n = a->num_rows;
-    if (a->row_offsets[0] != 0 || a->row_offsets[n] != a->num_nonzeros) {
-        set_error(w + "row_offsets inconsistent with num_nonzeros");
-        return MSPMV_ERR_INVALID;
-    }
-    for (int r = 0; r < n; ++r)
-        if (a->row_offsets[r + 1] < a->row_offsets[r]) {
-            set_error(w + "row_offsets not monotone");
-            return MSPMV_ERR_INVALID;
-        }
-    for (int i = 0; i < a->num_nonzeros; ++i)
-        if (a->column_indices[i] < 0 || a->column_indices[i] >= n) {
-            set_error(w + "column index out of range");
-            return MSPMV_ERR_INVALID;
-        }
     for (int i = 0; i < n; ++i) {
         int prev = -1;
         bool diag = false;
         for (int k = a->row_offsets[i]; k < a->row_offsets[i + 1]; ++k) {
-            if (a->column_indices[k] <= prev) {
-                set_error(w + "row " + std::to_string(i) + ": the columns must be strictly ascending");
-                return MSPMV_ERR_INVALID;
-            }
+            if (a->column_indices[k] <= prev)
+                return invalid(w + "row " + std::to_string(i) + ": the columns must be strictly ascending");
             prev = a->column_indices[k];
             diag = diag || prev == i;
         }
-        if (!diag) {
-            set_error(w + "row " + std::to_string(i) + " has no diagonal entry");
-            return MSPMV_ERR_INVALID;
-        }
+        if (!diag)
+            return invalid(w + "row " + std::to_string(i) + " has no diagonal entry");
     }
     return MSPMV_OK;
 }
@@ -76,10 +49,8 @@ extern "C" MSPMV_API mspmv_status mspmv_ilu0_values(const mspmv_csr_d *a, double
     mspmv_status st = mspmv::ilu0_check_rows(a, "ilu0");
     if (st != MSPMV_OK)
         return st;
-    if (a->num_nonzeros > 0 && !lu_values) {
-        mspmv::set_error("ilu0: null output");
-        return MSPMV_ERR_INVALID;
-    }
+    if (a->num_nonzeros > 0 && !lu_values)
+        return invalid("ilu0: null output");
     const int n = a->num_rows;
     const int *ro = a->row_offsets, *ci = a->column_indices;
     double *lu = lu_values;
@@ -112,4 +83,24 @@ extern "C" MSPMV_API mspmv_status mspmv_ilu0_values(const mspmv_csr_d *a, double
             pos[ci[k]] = -1;
     }
     return MSPMV_OK;
+}
+
+void mspmv::split_lu(int n, const int *ro, const int *ci, const double *va, bool unit_diag, HostFactor &f)
+{
+    const size_t cap = (size_t)ro[n] + (unit_diag ? (size_t)n : 0);
+    f.lro.assign((size_t)n + 1, 0), f.uro.assign((size_t)n + 1, 0);
+    f.lci.clear(), f.lva.clear(), f.uci.clear(), f.uva.clear();
+    f.lci.reserve(cap), f.lva.reserve(cap), f.uci.reserve(cap), f.uva.reserve(cap);
+    for (int i = 0; i < n; ++i) {
+        for (int k = ro[i]; k < ro[i + 1]; ++k) {
+            if (ci[k] < i)
+                f.lci.push_back(ci[k]), f.lva.push_back(va[k]);
+            else  // the diagonal first: the columns ascend
+                f.uci.push_back(ci[k]), f.uva.push_back(va[k]);
+        }
+        if (unit_diag)
+            f.lci.push_back(i), f.lva.push_back(1.0);
+        f.lro[(size_t)i + 1] = (int)f.lci.size();
+        f.uro[(size_t)i + 1] = (int)f.uci.size();
+    }
 }

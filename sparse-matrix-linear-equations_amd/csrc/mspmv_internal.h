@@ -1,9 +1,11 @@
 // mspmv_internal.h -- shared between the HIP translation units (the kernels files and the C-ABI
-// implementation, mspmv_api.hip).  Not installed; the public boundary is include/mspmv.h.
+// implementation, mspmv_api.hip and mspmv_tri.hip).  Not installed; the public boundary is include/mspmv.h.
+// What needs no HIP is mspmv_host.h, shared with the host-only .cpp files besides.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <map>
 #include <string>
 #include <type_traits>
@@ -11,6 +13,7 @@
 #include <vector>
 
 #include "mspmv.h"
+#include "mspmv_host.h"
 
 // hipMemset on the legacy null stream, then wait for it: every handle's stream is non-blocking, so a
 // null-stream fill is not ordered before the next launch on it otherwise (a fold's tickets or a plan's
@@ -247,7 +250,7 @@ struct ResidentCg {
 
 }  // namespace mspmv
 
-// Every handle and IC(0) factor gets a process-unique generation number at creation, so a cached
+// Every handle and triangular factor gets a process-unique generation number at creation, so a cached
 // CG graph that baked in another object's buffers is never replayed against a new object the
 // allocator happened to place at the same address (mspmv_api.hip, cg_solve_native).
 unsigned long long mspmv_next_generation();
@@ -354,25 +357,28 @@ struct PatternScope {
 };
 }  // namespace mspmv
 
-// IC(0) factor on the device (mspmv_ic0_create): L and its transpose for the two sync-free
-// triangular solves of the preconditioner apply, their level orders and the intermediate Y.
+namespace mspmv {
+
+// A triangular factor on the device (mspmv_tri.hip): a lower triangle solved forward and an upper one solved
+// backward, and the intermediate Y of an apply.  IC(0) keeps L (diagonal last in each row) and its transpose;
+// ILU(0) keeps L and U.  A natural-order factor (num_colors == 0) has its level orders and stores L's diagonal
+// (ILU(0): an explicit 1.0, so k_trsv_tagged divides by 1.0 exactly); its solves are the sync-free k_trsv_tagged.
 // A multi-colour factor (mspmv_ic0_create_colored, mspmv_ilu0_create_colored) is the factor of Ap = P A P^T in
-// the same slots, rows of a colour contiguous (the level orders upload_triangles builds are not used): colour c's
-// rows are [color_off[c], color_off[c + 1]), row i of Ap is row perm[i] of A.  Its solves are one k_trsv_color
-// launch per colour (mspmv_color.hip), never k_trsv_tagged.  IC(0) keeps L's diagonal, last in its row (l_diag);
-// ILU(0) keeps L strictly lower, its unit diagonal implied.
-struct mspmv_ic0_s {
+// the same slots, rows of a colour contiguous and no level orders: colour c's rows are
+// [color_off[c], color_off[c + 1]), row i of Ap is row perm[i] of A.  Its solves are one k_trsv_color launch per
+// colour (mspmv_color.hip), never k_trsv_tagged.  IC(0) keeps L's diagonal, last in its row (l_diag); ILU(0) keeps
+// L strictly lower, its unit diagonal implied.
+struct TriFactor {
     unsigned long long gen = mspmv_next_generation();
     int device = 0;
-    int n = 0, nnz = 0;
+    int n = 0;
     int *d_lro = nullptr, *d_lci = nullptr;  // L (lower, diagonal last in each row)
     double *d_lva = nullptr;
-    int *d_uro = nullptr, *d_uci = nullptr;  // L^T (upper, diagonal first)
+    int *d_uro = nullptr, *d_uci = nullptr;  // L^T or U (upper, diagonal first)
     double *d_uva = nullptr;
     int *d_fwd_order = nullptr;              // [n] rows of L by dependency level (then row): wave w solves row fwd_order[w]
-    int *d_bwd_order = nullptr;              // [n] rows of L^T by backward level
-    int levels_fwd = 0, levels_bwd = 0;
-    double *d_y = nullptr;                   // [n * L] forward-solve result
+    int *d_bwd_order = nullptr;              // [n] rows of the upper triangle by backward level
+    double *d_y = nullptr;                   // [n * L] forward-solve result (tri_workspace)
     size_t y_cap = 0;
     int num_colors = 0;                      // 0: a natural-order factor
     bool l_diag = false;                     // multi-colour: L's rows end in their diagonal (IC(0)), else it is implied
@@ -381,46 +387,45 @@ struct mspmv_ic0_s {
     int *d_perm = nullptr;
 };
 
-// ILU(0) factor on the device (mspmv_ilu0_create): two different triangles in mspmv_ic0_s's slots -- L (A's
-// strictly lower entries, then an explicit 1.0 diagonal, so k_trsv_tagged divides by 1.0 exactly) where IC(0)
-// keeps its L, and U (diagonal first) where IC(0) keeps L^T -- so launch_ic0_trsv runs unchanged; tri.d_y is
-// the intermediate of an apply.  A type of its own: a nonsymmetric factor is no argument of the PCG.
-// A multi-colour factor (mspmv_ilu0_create_colored) keeps L without its unit diagonal and U diagonal first, the
-// colours in tri.
-struct mspmv_ilu0_s {
-    mspmv_ic0_s tri;
+}  // namespace mspmv
+
+// The public header's opaque factors: two types, because a nonsymmetric factor is no argument of the PCG.
+struct mspmv_ic0_s : mspmv::TriFactor {};
+struct mspmv_ilu0_s : mspmv::TriFactor {
     double *d_hat = nullptr;  // [n * L] Phat, then Shat, of the running iteration (mspmv_bicgstab.hip)
     size_t hat_cap = 0;
 };
 
 namespace mspmv {
 
-// The host side of mspmv_ilu0_create_colored (mspmv_color.cpp): the checks, the ordering and the factor of the
-// permuted matrix, split into L (strictly lower) and U (diagonal first).
-mspmv_status ilu0_colored_host(const mspmv_csr_d *a, const int *colors, std::vector<int> &perm,
-                               std::vector<int> &color_off, std::vector<int> &lro, std::vector<int> &lci,
-                               std::vector<double> &lva, std::vector<int> &uro, std::vector<int> &uci,
-                               std::vector<double> &uva);
-// The host side of mspmv_ic0_create_colored: the same colour checks and ordering, then mspmv_ic0_factor of the
-// permuted matrix (L, diagonal last) and its mspmv_csr_transpose (diagonal first); *shift (nullable): the shift used.
-mspmv_status ic0_colored_host(const mspmv_csr_d *a, const int *colors, std::vector<int> &perm,
-                              std::vector<int> &color_off, std::vector<int> &lro, std::vector<int> &lci,
-                              std::vector<double> &lva, std::vector<int> &uro, std::vector<int> &uci,
-                              std::vector<double> &uva, double *shift);
-// One triangle of a multi-colour factor, in the colour ordering: X = L^-1 B (colours ascending) or U^-1 B
-// (descending), one launch per colour on s.  B and X are distinct panels.
-hipError_t launch_color_trsv(const mspmv_ic0_s *t, bool upper, const double *d_b, double *d_x, int L,
+// ---- triangular factors (mspmv_tri.hip) ----------------------------------------------
+// dst = M^-1 src with both triangles, through t->d_y (tri_workspace: n x L), on stream s -- the one place that
+// knows a multi-colour factor from a natural-order one for an apply.  Natural order: two sync-free solves
+// (k_trsv_tagged), each into a panel pre-filled with the pending pattern; a dependency that never arrives raises
+// ctrl->breakdown = 2 and ctrl->done.  Multi-colour: colour sweeps (k_trsv_color), 2 C for ILU(0), 2 C - 1 for
+// IC(0), src and dst in A's own ordering.
+hipError_t tri_apply(const TriFactor *t, const double *d_src, double *d_dst, int L, CgControl *ctrl, hipStream_t s);
+// One triangle alone: L X = B (which == 0) or U X = B; on a multi-colour factor in the colour ordering.
+hipError_t tri_solve(const TriFactor *t, int which, const double *d_b, double *d_x, int L, CgControl *ctrl,
+                     hipStream_t s);
+// A factor's n x L panels, grown on demand: the apply's intermediate d_y (the only place it grows; what: "IC(0)" /
+// "ILU(0)", for the error text) and, for the ILU(0) solver, the hat panel besides.
+mspmv_status tri_workspace(TriFactor *t, size_t elems, const char *what);
+mspmv_status ilu0_workspace(mspmv_ilu0_s *ilu, size_t elems);
+// Appends to a solver's graph key everything of the factor a captured apply bakes in: the factor, its generation,
+// the intermediate, both triangles' arrays, the ordering and the colour count.
+void tri_graph_key(const TriFactor *t, std::vector<const void *> &key);
+// The colour sweeps of a multi-colour factor (mspmv_color.hip), for tri_solve and tri_apply alone.  One triangle
+// in the colour ordering: X = L^-1 B (colours ascending) or U^-1 B (descending), one launch per colour on s; B and
+// X are distinct panels.
+hipError_t launch_color_trsv(const TriFactor *t, bool upper, const double *d_b, double *d_x, int L,
                              const CgControl *ctrl, hipStream_t s);
 // dst = P^T U^-1 L^-1 P src, in A's own ordering, through t->d_y (n x L): the forward sweeps gather src by perm
 // into d_y, the backward sweeps run in place on d_y and scatter into dst.  ILU(0): 2 C launches.  IC(0) (l_diag):
 // 2 C - 1, the last colour's forward launch dividing by the diagonal twice and scattering (its rows of L^T hold
 // the diagonal alone).
-hipError_t launch_color_apply(const mspmv_ic0_s *t, const double *d_src, double *d_dst, int L,
-                              const CgControl *ctrl, hipStream_t s);
-
-// Square, consistent CSR whose rows ascend strictly and hold their diagonal (mspmv_ilu0.cpp); else
-// MSPMV_ERR_INVALID, the message (prefixed with who) naming the first offending row.
-mspmv_status ilu0_check_rows(const mspmv_csr_d *a, const char *who);
+hipError_t launch_color_apply(const TriFactor *t, const double *d_src, double *d_dst, int L, const CgControl *ctrl,
+                              hipStream_t s);
 
 // ---- column-slab SpMV (mspmv_slab.hip) ---------------------------------------------
 constexpr int kSlabPlanKey = -1;
@@ -473,7 +478,6 @@ mspmv_status dia_plan_for(mspmv_handle_s *h, int L, const TilePlan **out);
 bool dia_dot_fused();     // the window SpMM takes p.Ap in its dot mode unless MSPMV_DIA_DOT=0 (mspmv_cg_passes.hip)
 
 // ---- launchers (mspmv_kernels.hip; the CG pieces below: mspmv_cg_passes.hip) ---------
-void set_error(const std::string &msg);
 hipError_t launch_merge_coords(const int *d_row_offsets, int m, int nnz, long long diag_step, int num_parts,
                                int2 *d_out, hipStream_t s);
 hipError_t launch_tile_modes(const int *d_row_offsets, const int2 *d_bounds, const unsigned char *d_split,
@@ -673,7 +677,7 @@ hipError_t launch_bicgstab_init(mspmv_handle_s *h, const double *d_b, double *d_
 hipError_t launch_bicgstab_iteration(mspmv_handle_s *h, const TilePlan &plan, const TilePlan *splan, double *d_x, int L,
                                      int nblk, double tol);
 // The same right-preconditioned with M = L U (ilu: the factor): Phat = U^-1 L^-1 P before the first product,
-// Shat = U^-1 L^-1 s before the second (both in ilu->d_hat, through ilu->tri.d_y), X advanced along them.
+// Shat = U^-1 L^-1 s before the second (both in ilu->d_hat, through ilu->d_y), X advanced along them.
 hipError_t launch_pbicgstab_iteration(mspmv_handle_s *h, mspmv_ilu0_s *ilu, const TilePlan &plan,
                                       const TilePlan *splan, double *d_x, int L, int nblk, double tol);
 // Iterations per CG batch / graph replay for an m-row, nnz-nonzero matrix and L columns (mspmv_api.hip).
@@ -793,13 +797,7 @@ hipError_t launch_pcg_init(mspmv_handle_s *h, mspmv_handle_s *hm, const TilePlan
 hipError_t launch_pcg_iteration(mspmv_handle_s *h, mspmv_handle_s *hm, const TilePlan &plan, const TilePlan &mplan,
                                 double *d_x, int L, int nblk, double tol);
 // IC(0)-preconditioned block CG (PCGSolveMultiple, work_2025/main/incomplete_cholesky.hpp:33-199):
-// Z = L^-T L^-1 R by two sync-free triangular solves (k_trsv_tagged); ic->d_y must hold m * L.
-// One sync-free triangular solve with the factor, on stream s: d_x (n x L) is filled with the pending
-// pattern, then k_trsv_tagged<L, fwd> solves L X = B (fwd) or L^T X = B.  A dependency that never
-// arrives raises ctrl->breakdown = 2 and ctrl->done.  The pass ic0_apply runs twice per application
-// and mspmv_ic0_solve_dev once.
-hipError_t launch_ic0_trsv(const mspmv_ic0_s *ic, bool fwd, const double *d_b, double *d_x, int L, CgControl *ctrl,
-                           hipStream_t s);
+// Z = L^-T L^-1 R by tri_apply; ic->d_y must hold m * L.
 hipError_t launch_pcg_ic0_init(mspmv_handle_s *h, mspmv_ic0_s *ic, const double *d_b, double *d_x, int L, double tol,
                                int nblk);
 hipError_t launch_pcg_ic0_iteration(mspmv_handle_s *h, mspmv_ic0_s *ic, const TilePlan &plan, double *d_x, int L,
@@ -808,5 +806,69 @@ hipError_t launch_pcg_ic0_iteration(mspmv_handle_s *h, mspmv_ic0_s *ic, const Ti
 // (every level of the tree: slots, slots/32, ... -> <= slots * 32/31 + one per level)
 inline size_t partials_capacity(size_t slots, int L) { return (slots + slots / (kSlotGroup - 1) + 8) * L; }
 inline size_t gtickets_capacity(size_t slots) { return (slots / (kSlotGroup - 1) + 8) * kTicketStride; }
+
+// ---- what the C-ABI translation units (mspmv_api.hip, mspmv_tri.hip) build their entry points from -----------
+// A failed HIP call / a failed step ends the entry point with its status (and HIP's text as the last error).
+#define HIP_TRY(expr)                                                                              \
+    do {                                                                                           \
+        hipError_t _e = (expr);                                                                    \
+        if (_e != hipSuccess) {                                                                    \
+            mspmv::set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                   \
+            return (_e == hipErrorOutOfMemory) ? MSPMV_ERR_OOM : MSPMV_ERR_HIP;                    \
+        }                                                                                          \
+    } while (0)
+
+#define ST_TRY(expr)                                                                               \
+    do {                                                                                           \
+        mspmv_status _s = (expr);                                                                  \
+        if (_s != MSPMV_OK)                                                                        \
+            return _s;                                                                             \
+    } while (0)
+
+template <typename T>
+inline mspmv_status dev_alloc(T **p, size_t count)
+{
+    *p = nullptr;
+    if (count == 0)
+        count = 1;
+    hipError_t e = hipMalloc((void **)p, count * sizeof(T));
+    if (e != hipSuccess) {
+        set_error(std::string("hipMalloc(") + std::to_string(count * sizeof(T)) + " B): " + hipGetErrorString(e));
+        *p = nullptr;
+        return e == hipErrorOutOfMemory ? MSPMV_ERR_OOM : MSPMV_ERR_HIP;
+    }
+    return MSPMV_OK;
+}
+
+template <typename T>
+inline void dev_free(T *&p)
+{
+    if (p)
+        (void)hipFree((void *)p);
+    p = nullptr;
+}
+
+inline bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
+
+inline mspmv_status check_handle(mspmv_handle h)
+{
+    if (!h)
+        return invalid("null handle");
+    HIP_TRY(hipSetDevice(h->device));
+    return MSPMV_OK;
+}
+
+inline mspmv_status validate_host_csr(const mspmv_csr_d *a)
+{
+    if (!a)
+        return invalid("null matrix");
+    if (a->num_rows < 0 || a->num_cols < 0 || a->num_nonzeros < 0)
+        return invalid("negative dimension");
+    if ((long long)a->num_rows + a->num_nonzeros > 0x7fffffffLL)
+        return invalid("num_rows + num_nonzeros must fit in int32 (merge-path diagonals)");
+    if (!a->row_offsets || (a->num_nonzeros > 0 && (!a->column_indices || !a->values)))
+        return invalid("null CSR array");
+    return MSPMV_OK;
+}
 
 }  // namespace mspmv

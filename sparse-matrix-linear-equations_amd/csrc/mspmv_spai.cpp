@@ -12,18 +12,12 @@
 // This is setup, not the hot path: the reference runs it once per matrix on the CPU, and so does
 // this library (OpenMP over columns); the PCG that applies M every iteration runs on the GPU
 // (mspmv_dpcg_spai_multi, two merge-path SpMMs per iteration).
-#include "mspmv.h"
+#include "mspmv_host.h"
 
 #include <omp.h>
 
 #include <cmath>
-#include <string>
 #include <utility>
-#include <vector>
-
-namespace mspmv {
-void set_error(const std::string &msg);
-}
 
 namespace {
 
@@ -76,32 +70,16 @@ bool householder_lstsq(int m, int n, double *A, double *b)
 
 extern "C" MSPMV_API mspmv_status mspmv_spai_values(const mspmv_csr_d *a, double *m_values)
 {
-    if (!a || !m_values || a->num_rows < 0 || a->num_cols < 0 || a->num_nonzeros < 0 ||
-        (a->num_nonzeros > 0 && (!a->row_offsets || !a->column_indices || !a->values))) {
-        mspmv::set_error("spai: bad arguments");
-        return MSPMV_ERR_INVALID;
-    }
-    if (a->num_rows != a->num_cols) {
-        mspmv::set_error("spai: the static-pattern SPAI needs a square matrix");
-        return MSPMV_ERR_INVALID;
-    }
+    mspmv_status st = mspmv::check_csr(a, "spai");
+    if (st != MSPMV_OK)
+        return st;
+    if (!m_values)
+        return mspmv::invalid("spai: bad arguments");
+    if (a->num_rows != a->num_cols)
+        return mspmv::invalid("spai: the static-pattern SPAI needs a square matrix");
     const int n = a->num_rows, nnz = a->num_nonzeros;
     const int *ro = a->row_offsets, *ci = a->column_indices;
     const double *va = a->values;
-    for (int r = 0; r < n; ++r)
-        if (ro[r + 1] < ro[r]) {
-            mspmv::set_error("spai: row_offsets not monotone");
-            return MSPMV_ERR_INVALID;
-        }
-    if (ro[0] != 0 || ro[n] != nnz) {
-        mspmv::set_error("spai: row_offsets inconsistent with num_nonzeros");
-        return MSPMV_ERR_INVALID;
-    }
-    for (int i = 0; i < nnz; ++i)
-        if (ci[i] < 0 || ci[i] >= n) {
-            mspmv::set_error("spai: column index out of range");
-            return MSPMV_ERR_INVALID;
-        }
     // CSC of A plus the CSC -> CSR position map (:84-119)
     std::vector<int> cptr((size_t)n + 1, 0), crow(nnz), cmap(nnz);
     std::vector<double> cval(nnz);

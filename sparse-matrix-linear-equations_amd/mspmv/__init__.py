@@ -724,45 +724,41 @@ def csr_transpose(a: CsrMatrix) -> CsrMatrix:
     return CsrMatrix.from_arrays(a.num_rows, ro, ci[: a.num_nonzeros], va[: a.num_nonzeros])
 
 
-class GpuIc0:
-    """An IC(0) factor L (and L^T) resident on a device for the GPU triangular solves.  GpuIc0.colored(A) builds
-    the multi-colour factor of A itself, whose solves are one parallel sweep per colour."""
+class _GpuTriFactor:
+    """What GpuIc0 and GpuIlu0 share: a factor's two triangles resident on a device (natural-order or
+    multi-colour), behind the C entry points mspmv_<_prefix>_*."""
 
-    def __init__(self, l: CsrMatrix, device: int = 0):
-        h = ctypes.c_void_p()
-        _check(lib.mspmv_ic0_create(ctypes.byref(l._c()), device, ctypes.byref(h)), "ic0_create")
+    _prefix = ""  # "ic0" / "ilu0"
+
+    def _call(self, name: str, *args) -> int:
+        where = f"{self._prefix}_{name}"
+        return _check(getattr(lib, "mspmv_" + where)(*args), where)
+
+    def _adopt(self, h, device: int, num_rows: int):
         self.h = h.value
         self.device = device
-        self.num_rows = l.num_rows
-        self.shift = None  # known to whoever factored l
+        self.num_rows = num_rows
         _track(self)
 
     @classmethod
-    def colored(cls, a: CsrMatrix, colors=None, device: int = 0) -> "GpuIc0":
-        """The multi-colour IC(0) factor of A (mspmv_ic0_create_colored): `colors` [n] (None: color_greedy's)
-        orders the rows colour after colour, and the factor is ic0_factor of the permuted matrix (.shift: the
-        diagonal shift it used).  Every check and the factorisation run on the host before the device is touched."""
+    def _create_colored(cls, a: CsrMatrix, colors, device: int, *extra):
+        """mspmv_<_prefix>_create_colored(a, colors, device, *extra, &handle) into a new object."""
         if colors is not None:
             colors = np.ascontiguousarray(colors, np.int32)
             if colors.shape != (a.num_rows,):
                 raise ValueError("colors must hold one colour per row")
         h = ctypes.c_void_p()
-        sh = ctypes.c_double()
-        _check(lib.mspmv_ic0_create_colored(ctypes.byref(a._c()), None if colors is None else _ptr(colors), device,
-                                            ctypes.byref(sh), ctypes.byref(h)), "ic0_create_colored")
         self = cls.__new__(cls)
-        self.h = h.value
-        self.device = device
-        self.num_rows = a.num_rows
-        self.shift = sh.value
-        _track(self)
+        self._call("create_colored", ctypes.byref(a._c()), None if colors is None else _ptr(colors), device, *extra,
+                   ctypes.byref(h))
+        self._adopt(h, device, a.num_rows)
         return self
 
     @property
     def num_colors(self) -> int:
         """The factor's colours; 0 for a natural-order factor."""
         num = ctypes.c_int()
-        _check(lib.mspmv_ic0_colors(self.h, ctypes.byref(num), None), "ic0_colors")
+        self._call("colors", self.h, ctypes.byref(num), None)
         return num.value
 
     @property
@@ -772,53 +768,42 @@ class GpuIc0:
             return None
         num = ctypes.c_int()
         perm = np.zeros(max(self.num_rows, 1), np.int32)
-        _check(lib.mspmv_ic0_colors(self.h, ctypes.byref(num), _ptr(perm)), "ic0_colors")
+        self._call("colors", self.h, ctypes.byref(num), _ptr(perm))
         return perm[: self.num_rows]
 
+    def _on_host_panel(self, B: np.ndarray, run) -> np.ndarray:
+        """run(dB, dX, L) on device copies of a host panel B [n] or [n, L]; X in B's shape."""
+        B = np.ascontiguousarray(B, np.float64)
+        shape = B.shape
+        if B.ndim == 1:
+            B = B[:, None]
+        dB = DeviceBuffer.from_array(B, self.device) if B.size else DeviceBuffer(16, self.device)
+        dX = DeviceBuffer(max(B.nbytes, 16), self.device)
+        try:
+            run(dB, dX, B.shape[1])
+            return dX.download(B.shape).reshape(shape)
+        finally:
+            dB.free()
+            dX.free()
+
     def apply_dev(self, g: "GpuCsr", dB: "DeviceBuffer", dX: "DeviceBuffer", L: int) -> int:
-        """mspmv_ic0_apply_dev on device panels: X = L^-T L^-1 B in A's own ordering."""
-        return _check(lib.mspmv_ic0_apply_dev(g.h, self.h, dB.ptr, dX.ptr, L), "ic0_apply_dev")
+        """mspmv_<_prefix>_apply_dev on device panels: X = M^-1 B (both triangles) in A's own ordering."""
+        return self._call("apply_dev", g.h, self.h, dB.ptr, dX.ptr, L)
 
     def apply(self, g: "GpuCsr", B: np.ndarray) -> np.ndarray:
-        """The preconditioner apply X = M^-1 B on g's stream (mspmv_ic0_apply_dev), for either kind of factor:
+        """The preconditioner apply X = M^-1 B on g's stream (apply_dev), for either kind of factor:
         a host panel B [n] or [n, L], L in SUPPORTED_L, in A's own ordering."""
-        B = np.ascontiguousarray(B, np.float64)
-        shape = B.shape
-        if B.ndim == 1:
-            B = B[:, None]
-        dB = DeviceBuffer.from_array(B, self.device) if B.size else DeviceBuffer(16, self.device)
-        dX = DeviceBuffer(max(B.nbytes, 16), self.device)
-        try:
-            self.apply_dev(g, dB, dX, B.shape[1])
-            return dX.download(B.shape).reshape(shape)
-        finally:
-            dB.free()
-            dX.free()
+        return self._on_host_panel(B, lambda dB, dX, L: self.apply_dev(g, dB, dX, L))
 
-    def solve_dev(self, g: "GpuCsr", dB: "DeviceBuffer", dX: "DeviceBuffer", L: int, transpose: bool = False) -> int:
-        """mspmv_ic0_solve_dev on device panels: one triangular solve, L X = B or L^T X = B."""
-        return _check(lib.mspmv_ic0_solve_dev(g.h, self.h, int(bool(transpose)), dB.ptr, dX.ptr, L), "ic0_solve_dev")
+    def _solve_dev(self, g, dB, dX, L: int, second: bool) -> int:
+        return self._call("solve_dev", g.h, self.h, int(bool(second)), dB.ptr, dX.ptr, L)
 
-    def solve(self, g: "GpuCsr", B: np.ndarray, transpose: bool = False) -> np.ndarray:
-        """One triangular solve with the factor on g's stream (mspmv_ic0_solve_dev): X with L X = B, or
-        L^T X = B (transpose), for a host panel B [n] or [n, L], L in SUPPORTED_L.  On a multi-colour factor the
-        triangle is the permuted matrix's, B and X in the colour ordering."""
-        B = np.ascontiguousarray(B, np.float64)
-        shape = B.shape
-        if B.ndim == 1:
-            B = B[:, None]
-        dB = DeviceBuffer.from_array(B, self.device) if B.size else DeviceBuffer(16, self.device)
-        dX = DeviceBuffer(max(B.nbytes, 16), self.device)
-        try:
-            self.solve_dev(g, dB, dX, B.shape[1], transpose)
-            return dX.download(B.shape).reshape(shape)
-        finally:
-            dB.free()
-            dX.free()
+    def _solve(self, g, B: np.ndarray, second: bool) -> np.ndarray:
+        return self._on_host_panel(B, lambda dB, dX, L: self._solve_dev(g, dB, dX, L, second))
 
     def close(self):
         if getattr(self, "h", None):
-            lib.mspmv_ic0_destroy(self.h)
+            self._call("destroy", self.h)
             self.h = None
 
     def __del__(self):
@@ -832,6 +817,39 @@ class GpuIc0:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class GpuIc0(_GpuTriFactor):
+    """An IC(0) factor L (and L^T) resident on a device for the GPU triangular solves.  GpuIc0.colored(A) builds
+    the multi-colour factor of A itself, whose solves are one parallel sweep per colour."""
+
+    _prefix = "ic0"
+
+    def __init__(self, l: CsrMatrix, device: int = 0):
+        h = ctypes.c_void_p()
+        self._call("create", ctypes.byref(l._c()), device, ctypes.byref(h))
+        self._adopt(h, device, l.num_rows)
+        self.shift = None  # known to whoever factored l
+
+    @classmethod
+    def colored(cls, a: CsrMatrix, colors=None, device: int = 0) -> "GpuIc0":
+        """The multi-colour IC(0) factor of A (mspmv_ic0_create_colored): `colors` [n] (None: color_greedy's)
+        orders the rows colour after colour, and the factor is ic0_factor of the permuted matrix (.shift: the
+        diagonal shift it used).  Every check and the factorisation run on the host before the device is touched."""
+        sh = ctypes.c_double()
+        self = cls._create_colored(a, colors, device, ctypes.byref(sh))
+        self.shift = sh.value
+        return self
+
+    def solve_dev(self, g: "GpuCsr", dB: "DeviceBuffer", dX: "DeviceBuffer", L: int, transpose: bool = False) -> int:
+        """mspmv_ic0_solve_dev on device panels: one triangular solve, L X = B or L^T X = B."""
+        return self._solve_dev(g, dB, dX, L, transpose)
+
+    def solve(self, g: "GpuCsr", B: np.ndarray, transpose: bool = False) -> np.ndarray:
+        """One triangular solve with the factor on g's stream (mspmv_ic0_solve_dev): X with L X = B, or
+        L^T X = B (transpose), for a host panel B [n] or [n, L], L in SUPPORTED_L.  On a multi-colour factor the
+        triangle is the permuted matrix's, B and X in the colour ordering."""
+        return self._solve(g, B, transpose)
 
 
 def pcg_ic0(g: "GpuCsr", ic: GpuIc0, B: np.ndarray, max_iters: int, tolerance: float, hist_cap: int = 0):
@@ -881,111 +899,34 @@ def csr_permute_sym(a: CsrMatrix, perm) -> CsrMatrix:
     return CsrMatrix.from_arrays(a.num_cols, ro, ci[: a.num_nonzeros], va[: a.num_nonzeros])
 
 
-class GpuIlu0:
+class GpuIlu0(_GpuTriFactor):
     """An ILU(0) factor (L with unit diagonal, and U) resident on a device for the GPU triangular solves.
     `lu`: A's pattern with ilu0_values(A).  GpuIlu0.colored(A) builds the multi-colour factor of A itself,
     whose solves are one parallel sweep per colour."""
 
+    _prefix = "ilu0"
+
     def __init__(self, lu: CsrMatrix, device: int = 0):
         h = ctypes.c_void_p()
-        _check(lib.mspmv_ilu0_create(ctypes.byref(lu._c()), device, ctypes.byref(h)), "ilu0_create")
-        self.h = h.value
-        self.device = device
-        _track(self)
+        self._call("create", ctypes.byref(lu._c()), device, ctypes.byref(h))
+        self._adopt(h, device, lu.num_rows)
 
     @classmethod
     def colored(cls, a: CsrMatrix, colors=None, device: int = 0) -> "GpuIlu0":
         """The multi-colour ILU(0) factor of A (mspmv_ilu0_create_colored): `colors` [n] (None: color_greedy's)
         orders the rows colour after colour, and the factor is ILU(0) of the permuted matrix.  Every check and
         the factorisation run on the host before the device is touched."""
-        if colors is not None:
-            colors = np.ascontiguousarray(colors, np.int32)
-            if colors.shape != (a.num_rows,):
-                raise ValueError("colors must hold one colour per row")
-        h = ctypes.c_void_p()
-        _check(lib.mspmv_ilu0_create_colored(ctypes.byref(a._c()), None if colors is None else _ptr(colors), device,
-                                             ctypes.byref(h)), "ilu0_create_colored")
-        self = cls.__new__(cls)
-        self.h = h.value
-        self.device = device
-        self.num_rows = a.num_rows
-        _track(self)
-        return self
-
-    @property
-    def num_colors(self) -> int:
-        """The factor's colours; 0 for a natural-order factor."""
-        num = ctypes.c_int()
-        _check(lib.mspmv_ilu0_colors(self.h, ctypes.byref(num), None), "ilu0_colors")
-        return num.value
-
-    @property
-    def perm(self):
-        """Row i of the permuted matrix is row perm[i] of A (int32 [n]); None for a natural-order factor."""
-        if self.num_colors == 0:
-            return None
-        num = ctypes.c_int()
-        perm = np.zeros(max(self.num_rows, 1), np.int32)
-        _check(lib.mspmv_ilu0_colors(self.h, ctypes.byref(num), _ptr(perm)), "ilu0_colors")
-        return perm[: self.num_rows]
-
-    def apply_dev(self, g: "GpuCsr", dB: "DeviceBuffer", dX: "DeviceBuffer", L: int) -> int:
-        """mspmv_ilu0_apply_dev on device panels: X = U^-1 L^-1 B in A's own ordering."""
-        return _check(lib.mspmv_ilu0_apply_dev(g.h, self.h, dB.ptr, dX.ptr, L), "ilu0_apply_dev")
-
-    def apply(self, g: "GpuCsr", B: np.ndarray) -> np.ndarray:
-        """The preconditioner apply X = M^-1 B on g's stream (mspmv_ilu0_apply_dev), for either kind of factor:
-        a host panel B [n] or [n, L], L in SUPPORTED_L, in A's own ordering."""
-        B = np.ascontiguousarray(B, np.float64)
-        shape = B.shape
-        if B.ndim == 1:
-            B = B[:, None]
-        dB = DeviceBuffer.from_array(B, self.device) if B.size else DeviceBuffer(16, self.device)
-        dX = DeviceBuffer(max(B.nbytes, 16), self.device)
-        try:
-            self.apply_dev(g, dB, dX, B.shape[1])
-            return dX.download(B.shape).reshape(shape)
-        finally:
-            dB.free()
-            dX.free()
+        return cls._create_colored(a, colors, device)
 
     def solve_dev(self, g: "GpuCsr", dB: "DeviceBuffer", dX: "DeviceBuffer", L: int, upper: bool = False) -> int:
         """mspmv_ilu0_solve_dev on device panels: one triangular solve, L X = B or U X = B."""
-        return _check(lib.mspmv_ilu0_solve_dev(g.h, self.h, int(bool(upper)), dB.ptr, dX.ptr, L), "ilu0_solve_dev")
+        return self._solve_dev(g, dB, dX, L, upper)
 
     def solve(self, g: "GpuCsr", B: np.ndarray, upper: bool = False) -> np.ndarray:
         """One triangular solve with the factor on g's stream (mspmv_ilu0_solve_dev): X with L X = B, or
         U X = B (upper), for a host panel B [n] or [n, L], L in SUPPORTED_L.  On a multi-colour factor the
         triangle is the permuted matrix's, B and X in the colour ordering."""
-        B = np.ascontiguousarray(B, np.float64)
-        shape = B.shape
-        if B.ndim == 1:
-            B = B[:, None]
-        dB = DeviceBuffer.from_array(B, self.device) if B.size else DeviceBuffer(16, self.device)
-        dX = DeviceBuffer(max(B.nbytes, 16), self.device)
-        try:
-            self.solve_dev(g, dB, dX, B.shape[1], upper)
-            return dX.download(B.shape).reshape(shape)
-        finally:
-            dB.free()
-            dX.free()
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib.mspmv_ilu0_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        return self._solve(g, B, upper)
 
 
 def pbicgstab_ilu0(g: "GpuCsr", m: GpuIlu0, B: np.ndarray, max_iters: int, tolerance: float, hist_cap: int = 0,

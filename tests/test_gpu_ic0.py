@@ -1,4 +1,4 @@
-"""The IC(0) triangular solves on their own (mspmv_ic0_solve_dev: the pass ic0_apply runs twice per
+"""The IC(0) triangular solves on their own (mspmv_ic0_solve_dev: the pass tri_apply runs twice per
 preconditioner application), on factors no stencil gives -- tests/ic0_cases.py: random rows, hub rows
 as long as the matrix, a 2,000-deep chain, a grid of more waves than the device holds at once.
 

@@ -87,7 +87,7 @@ def test_apply_on_a_natural_order_factor_is_its_two_solves(mspmv, name, L):
     n = len(mc.matrix(name)[0]) - 1
     B = panel(n, L, 5000 + L)
     with tg.Solver(mspmv, name) as s:
-        assert s.m.num_colors == 0 and s.m.perm is None
+        assert s.m.num_colors == 0 and s.m.perm is None and s.m.num_rows == n
         Z = s.m.apply(s.g, B)
         want = s.m.solve(s.g, s.m.solve(s.g, B, upper=False), upper=True)
     np.testing.assert_array_equal(Z, want)
