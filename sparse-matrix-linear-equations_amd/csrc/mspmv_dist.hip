@@ -118,9 +118,7 @@ struct mspmv_dist_s {
     // captured once into a graph and replayed per batch while the key (buffers, plans, L, tolerance,
     // history size, K) is unchanged.  Captured only after one eager batch has run on this object,
     // so RCCL has set up its connections outside the capture.
-    hipGraph_t cg_graph = nullptr;
-    hipGraphExec_t cg_exec = nullptr;
-    std::vector<const void *> cg_key;
+    GraphCache cg;
     bool cg_warm = false;
     // test hook (mspmv_dist_test_poison_tickets): the next CG solve's fold tickets start dirty
     unsigned poison_value = 0;
@@ -233,10 +231,7 @@ mspmv_status mspmv_dist_destroy(mspmv_dist d)
     dfree(d->d_hist);
     if (d->h_ctrl)
         (void)hipHostFree(d->h_ctrl);
-    if (d->cg_exec)
-        (void)hipGraphExecDestroy(d->cg_exec);
-    if (d->cg_graph)
-        (void)hipGraphDestroy(d->cg_graph);
+    d->cg.reset();
     for (auto &ph : d->part)
         if (ph)
             mspmv_destroy(ph);
@@ -574,7 +569,7 @@ mspmv_status halo_exchange(mspmv_dist_s *d, int L, const CgControl *ctrl)
 mspmv_status get_local_plan(mspmv_dist_s *d, int L, const TilePlan **plan)
 {
     // the plan the local handle's kernels use for L (the node-block plan for L > 1 on FEM blocks)
-    return plan_for(d->local, L, plan);
+    return solver_plan(d->local, L, plan);
 }
 
 }  // namespace
@@ -763,11 +758,11 @@ static mspmv_status dist_cg_native(mspmv_dist d, const double *d_B_own, double *
     int toff[4] = {0, 0, 0, 0};
     const bool split = d->part[1] != nullptr;
     if (dia_dot_fused() && !split)
-        D_ST(dia_plan_for(d->local, L, &dlocal));
+        D_ST(window_plan(d->local, L, &dlocal));
     for (int q = 0; q < 3 && split; ++q) {
-        D_ST(plan_for(d->part[q], L, &pp[q]));
+        D_ST(solver_plan(d->part[q], L, &pp[q]));
         if (dia_dot_fused())
-            D_ST(dia_plan_for(d->part[q], L, &dpart[q]));
+            D_ST(window_plan(d->part[q], L, &dpart[q]));
         toff[q + 1] = toff[q] + (dpart[q] ? dpart[q]->num_tiles : pp[q]->num_tiles);
     }
     D_ST(ensure_buffers(d, L, nblk, std::max({plan->num_tiles, dlocal ? dlocal->num_tiles : 0, toff[3]}), cap));
@@ -885,33 +880,24 @@ static mspmv_status dist_cg_native(mspmv_dist d, const double *d_B_own, double *
     // one batch: the cached graph when it matches (capturing it now if this object has run an eager
     // batch before), else the iterations enqueued one by one
     auto batch = [&](int k) -> mspmv_status {
-        if (use_graph && k == K && d->cg_warm && (!d->cg_exec || d->cg_key != key)) {
-            if (d->cg_exec)
-                (void)hipGraphExecDestroy(d->cg_exec);
-            if (d->cg_graph)
-                (void)hipGraphDestroy(d->cg_graph);
-            d->cg_exec = nullptr;
-            d->cg_graph = nullptr;
-            d->cg_key.clear();
+        if (use_graph && k == K && d->cg_warm && (!d->cg.exec || d->cg.key != key)) {
+            d->cg.reset();
             hipError_t e = hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed);
             mspmv_status cst = e == hipSuccess ? MSPMV_OK : MSPMV_ERR_HIP;
             for (int i = 0; i < K && cst == MSPMV_OK; ++i)
                 cst = iteration();
             hipGraph_t g = nullptr;
             const hipError_t e2 = e == hipSuccess ? hipStreamEndCapture(s, &g) : e;
-            d->cg_graph = g;
+            d->cg.graph = g;
             if (cst == MSPMV_OK && e2 == hipSuccess &&
-                hipGraphInstantiate(&d->cg_exec, g, nullptr, nullptr, 0) == hipSuccess) {
-                d->cg_key = key;
+                hipGraphInstantiate(&d->cg.exec, g, nullptr, nullptr, 0) == hipSuccess) {
+                d->cg.key = key;
                 if (getenv("MSPMV_DEBUG_GRAPH"))
                     fprintf(stderr, "mspmv: dist CG batch of %d iterations captured (rank %d)\n", K, d->rank);
             } else {
                 fprintf(stderr, "mspmv: dist CG batch capture failed (rank %d): batches run eagerly\n", d->rank);
                 // capture unsupported here (or failed): this object runs its batches eagerly from now on
-                if (d->cg_graph)
-                    (void)hipGraphDestroy(d->cg_graph);
-                d->cg_graph = nullptr;
-                d->cg_exec = nullptr;
+                d->cg.reset();
                 d->cg_warm = false;
                 (void)hipGetLastError();
                 // whatever failed inside the capture (HIP or RCCL), this batch still runs eagerly
@@ -920,8 +906,8 @@ static mspmv_status dist_cg_native(mspmv_dist d, const double *d_B_own, double *
                 (void)cst;
             }
         }
-        if (use_graph && k == K && d->cg_exec && d->cg_key == key)
-            return hipGraphLaunch(d->cg_exec, s) == hipSuccess ? MSPMV_OK
+        if (use_graph && k == K && d->cg.exec && d->cg.key == key)
+            return hipGraphLaunch(d->cg.exec, s) == hipSuccess ? MSPMV_OK
                                                                : fail_msg(MSPMV_ERR_HIP, "dist CG: graph launch failed");
         for (int i = 0; i < k; ++i)
             D_ST(iteration_hook());

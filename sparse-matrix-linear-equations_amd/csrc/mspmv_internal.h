@@ -1,5 +1,6 @@
 // mspmv_internal.h -- shared between the HIP translation units (the kernels files and the C-ABI
-// implementation, mspmv_api.hip and mspmv_tri.hip).  Not installed; the public boundary is include/mspmv.h.
+// implementation: mspmv_api.hip, mspmv_plan.hip, mspmv_solve.hip and mspmv_tri.hip).  Not installed; the public
+// boundary is include/mspmv.h.
 // What needs no HIP is mspmv_host.h, shared with the host-only .cpp files besides.
 #pragma once
 
@@ -252,8 +253,28 @@ struct ResidentCg {
 
 // Every handle and triangular factor gets a process-unique generation number at creation, so a cached
 // CG graph that baked in another object's buffers is never replayed against a new object the
-// allocator happened to place at the same address (mspmv_api.hip, cg_solve_native).
+// allocator happened to place at the same address (mspmv_solve.hip, cg_solve_native).
 unsigned long long mspmv_next_generation();
+
+namespace mspmv {
+// A solver's cached iteration graph: K iterations captured from the handle's stream, reused while everything it
+// was captured with (the key) is unchanged (instantiation costs ms).
+struct GraphCache {
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    std::vector<const void *> key;
+    void reset()
+    {
+        if (exec)
+            (void)hipGraphExecDestroy(exec);
+        if (graph)
+            (void)hipGraphDestroy(graph);
+        exec = nullptr;
+        graph = nullptr;
+        key.clear();
+    }
+};
+}  // namespace mspmv
 
 struct mspmv_handle_s {
     unsigned long long gen = mspmv_next_generation();
@@ -298,18 +319,9 @@ struct mspmv_handle_s {
     // test hook (mspmv_test_poison_tickets): the next CG solve fills its fold tickets with this value
     unsigned poison_value = 0;
     int poison_flags = 0;  // 0: none pending; MSPMV_POISON_* bits
-    // CG iteration graph (K iterations), reused while everything it was captured with is unchanged
-    hipGraph_t cg_graph = nullptr;
-    hipGraphExec_t cg_exec = nullptr;
-    std::vector<const void *> cg_graph_key;
-    // ... and BiCGSTAB's (bicgstab_solve_native), cached apart so neither solver evicts the other's
-    hipGraph_t bicg_graph = nullptr;
-    hipGraphExec_t bicg_exec = nullptr;
-    std::vector<const void *> bicg_graph_key;
-    // ... and the ILU(0)-preconditioned BiCGSTAB's (pbicgstab_solve_native): the same workspace, other launches
-    hipGraph_t pbicg_graph = nullptr;
-    hipGraphExec_t pbicg_exec = nullptr;
-    std::vector<const void *> pbicg_graph_key;
+    // CG's iteration graph; BiCGSTAB's (bicgstab_solve_native), cached apart so neither solver evicts the
+    // other's; and the ILU(0)-preconditioned BiCGSTAB's: the same workspace, other launches
+    mspmv::GraphCache cg_graph, bicg_graph, pbicg_graph;
     // timing
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double last_tile_kernel_ms = 0.0;
@@ -321,19 +333,19 @@ struct mspmv_handle_s {
     // the kernel the last BiCGSTAB solve's two products ran (mspmv_solver_product_kernel_name)
     std::string last_solver_product;
     // plain single-RHS SpMV on one-wave tiles (a plan of its own, TilePlan::lanes = 64): -1 not
-    // decided yet, 0 no, 1 yes (mspmv_api.hip spmv_plan: skewed rows, most tiles merge walks)
+    // decided yet, 0 no, 1 yes (mspmv_plan.hip spmv_plan: skewed rows, most tiles merge walks)
     int spmv_onewave = -1;
     // plain single-RHS SpMV on the column-slab plan (mspmv_slab.hip, plan key kSlabPlanKey): -1 not
     // decided yet, 0 no, 1 yes (spmv_plan; MSPMV_SPMV_SLAB)
     int spmv_slab = -1;
-    // plain single-RHS SpMV on the run-balanced node-block plan (key kRunPlanKey; mspmv_api.hip
+    // plain single-RHS SpMV on the run-balanced node-block plan (key kRunPlanKey; mspmv_plan.hip
     // spmv_runs_decide): -1 not decided yet, 0 no, 1 yes
     int spmv_runs = -1;
     // plain SpMM of width L (index l_index(L)) on a column-slab plan (key slab_mm_key(L)): -1 not
-    // decided yet, 0 no, 1 yes (mspmv_api.hip spmm_slab_decide; MSPMV_SPMM_SLAB)
+    // decided yet, 0 no, 1 yes (mspmv_plan.hip spmm_slab_decide; MSPMV_SPMM_SLAB)
     int spmm_slab[5] = {-1, -1, -1, -1, -1};
     // plain SpMV / SpMM (every width) and the split CG's SpMM on the offset-window plan (key kDiaPlanKey;
-    // mspmv_api.hip dia_decide): -1 not decided yet, 0 no, 1 yes
+    // mspmv_plan.hip dia_decide): -1 not decided yet, 0 no, 1 yes.  drop_plans sets all of these back.
     int dia = -1;
 };
 
@@ -429,7 +441,7 @@ hipError_t launch_color_apply(const TriFactor *t, const double *d_src, double *d
 
 // ---- column-slab SpMV (mspmv_slab.hip) ---------------------------------------------
 constexpr int kSlabPlanKey = -1;
-constexpr int kRunPlanKey = -2;  // the run-balanced node-block SpMV plan (mspmv_api.hip spmv_runs_decide)
+constexpr int kRunPlanKey = -2;  // the run-balanced node-block SpMV plan (mspmv_plan.hip spmv_runs_decide)
 // Builds the column-slab plan into *p (blocks, split rows, reordered stream); MSPMV_ERR_UNSUPPORTED
 // when the matrix does not fit the form (rows per block) or its blocks would hold fewer than
 // min_nnz_per_block nonzeros on average; p is freed by the caller on any error.
@@ -472,9 +484,7 @@ hipError_t launch_cg1_dia(mspmv_handle_s *h, const TilePlan &plan, const double 
 // ... and on the merge-path tiles of `plan` (mspmv_kernels.hip, k_spmv_tile MODE 1): one p.Ap partial per tile.
 hipError_t launch_cg1_tile(mspmv_handle_s *h, const TilePlan &plan, const double *rp_old, double *rp_new, double *d_x,
                            int parity, int nblk, double tol, int *nslots);
-bool dia_spmm_enabled();  // the L-wide products on the windows too unless MSPMV_DIA_SPMM=0 (mspmv_api.hip)
-// The handle's offset-window plan for width L (decided on first use), or null (mspmv_api.hip)
-mspmv_status dia_plan_for(mspmv_handle_s *h, int L, const TilePlan **out);
+bool dia_spmm_enabled();  // the L-wide products on the windows too unless MSPMV_DIA_SPMM=0 (mspmv_plan.hip)
 bool dia_dot_fused();     // the window SpMM takes p.Ap in its dot mode unless MSPMV_DIA_DOT=0 (mspmv_cg_passes.hip)
 
 // ---- launchers (mspmv_kernels.hip; the CG pieces below: mspmv_cg_passes.hip) ---------
@@ -680,7 +690,7 @@ hipError_t launch_bicgstab_iteration(mspmv_handle_s *h, const TilePlan &plan, co
 // Shat = U^-1 L^-1 s before the second (both in ilu->d_hat, through ilu->d_y), X advanced along them.
 hipError_t launch_pbicgstab_iteration(mspmv_handle_s *h, mspmv_ilu0_s *ilu, const TilePlan &plan,
                                       const TilePlan *splan, double *d_x, int L, int nblk, double tol);
-// Iterations per CG batch / graph replay for an m-row, nnz-nonzero matrix and L columns (mspmv_api.hip).
+// Iterations per CG batch / graph replay for an m-row, nnz-nonzero matrix and L columns.
 int cg_batch_iters(long long m, long long nnz, int L);
 // Pipelined single-RHS CG (L == 1 unless MSPMV_CG_SPLIT=1): init (x = 0, r = p0 = b, b.b
 // partials) and, after the loop, the last stop test (after max_iters iterations) and the last deferred
@@ -775,8 +785,28 @@ hipError_t launch_spmm_dot_tiles(mspmv_handle_s *h, const TilePlan &plan, const 
                                  CgControl *ctrl, double *partials, hipStream_t s, long long row_off);
 hipError_t launch_fold_dot(int T, int L, double *partials, unsigned *gtickets, double *dot_out, CgScalars *scal,
                            const unsigned char *conv, CgControl *ctrl, int fold_mode, hipStream_t s);
-// The tile plan a handle's kernels use for L right-hand sides (built on first use).
-mspmv_status plan_for(mspmv_handle_s *h, int L, const TilePlan **out);
+// ---- plans (mspmv_plan.hip): built and decided on first use, cached on the handle ----
+// The solvers' plan for L right-hand sides (CG, BiCGSTAB, dot-mode and sharded callers): the workgroup tile plan
+// for width L, or for L > 1 the single-RHS plan when it is all register node blocks.
+mspmv_status solver_plan(mspmv_handle_s *h, int L, const TilePlan **out);
+// The plain product's (y = A x / Y = A X): offset windows; for L = 1 a slab / sliced-ELL, one-wave or
+// run-balanced plan; for L > 1 the node-block or run-balanced plan, for L = 8 / 16 a slab-MM plan; else the
+// solvers' plan.
+mspmv_status product_plan(mspmv_handle_s *h, int L, const TilePlan **out);
+// The handle's offset-window plan for a product of width L, or null.
+mspmv_status window_plan(mspmv_handle_s *h, int L, const TilePlan **out);
+void free_plan(TilePlan &p);
+// Frees every cached plan and sets every plan decision back to "not decided".  Only after the handle's stream
+// has been synchronised.
+void drop_plans(mspmv_handle_s *h);
+// Widest native width (the tile kernels' L in {1, 2, 4, 8, 16}) that fits `left` columns.
+inline int native_chunk(int left)
+{
+    int w = 16;
+    while (w > left)
+        w >>= 1;
+    return w;
+}
 // mspmv_csr_create on a stream the caller owns (kept; the handle never destroys it)
 mspmv_status csr_create_on_stream(const mspmv_csr_d *host, int device, hipStream_t stream, mspmv_handle *out);
 // Rows [row_lo, row_hi) of `parent` as a handle of their own (own stream, row offsets and plans) whose
@@ -807,7 +837,7 @@ hipError_t launch_pcg_ic0_iteration(mspmv_handle_s *h, mspmv_ic0_s *ic, const Ti
 inline size_t partials_capacity(size_t slots, int L) { return (slots + slots / (kSlotGroup - 1) + 8) * L; }
 inline size_t gtickets_capacity(size_t slots) { return (slots / (kSlotGroup - 1) + 8) * kTicketStride; }
 
-// ---- what the C-ABI translation units (mspmv_api.hip, mspmv_tri.hip) build their entry points from -----------
+// ---- what the C-ABI translation units (mspmv_api.hip, mspmv_solve.hip, mspmv_tri.hip) build their entries from -----
 // A failed HIP call / a failed step ends the entry point with its status (and HIP's text as the last error).
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \

@@ -2446,7 +2446,7 @@ int spmv_items_per_thread() { return kSpmvIpt; }
 // workgroups per CU instead of 7, r04aa).
 int spmm_iptg_for(int L) { return L >= 16 ? 32 : L >= 8 ? 24 : 8; }
 
-// The kernel a plain SpMM of native width L (1, 2, 4, 8, 16) launches on `plan` (get_plan's
+// The kernel a plain SpMM of native width L (1, 2, 4, 8, 16) launches on `plan` (product_plan's
 // choice for L), spelled as rocprofv3 lists it: launch_spmm_L's dispatch, restated.
 std::string spmm_kernel_name(const mspmv_handle_s *h, const TilePlan &plan, int L)
 {
@@ -2659,7 +2659,7 @@ static TileArgs make_args(mspmv_handle_s *h, const TilePlan &plan, const double 
         a.blk_stride = plan.blk_stride;
         a.pcols = plan.d_pcols;
         a.recs = plan.d_recs;
-        // L > 1 runs the node-block plan only while k_spmm_blk is enabled (get_plan's gate): L = 2
+        // L > 1 runs the node-block plan only while k_spmm_blk is enabled (all_node_blocks' gate, mspmv_plan.hip): L = 2
         // shares the single-RHS tile size, so without this the switched-off plan would still be all-reg
         a.all_reg = plan.d_blk && plan.num_tiles_reg == plan.num_tiles && (L == 1 || spmm_blk_enabled());
         a.blk_spmv = L == 1 && plan.blk_spmv;
@@ -2789,7 +2789,7 @@ hipError_t launch_spmm_tile_only(mspmv_handle_s *h, const TilePlan &plan, const 
         return hipSuccess;
     if (plan.dia)  // offset windows: every width on one plan
         return launch_dia(h, plan, d_X, d_Y, L, ld, ctrl);
-    if (plan.slab) {  // a column-slab plan: the plain SpMV's (spmv_plan) or an L-wide SpMM's (get_plan)
+    if (plan.slab) {  // a column-slab plan: the plain SpMV's (spmv_plan) or an L-wide SpMM's (product_plan)
         if (plan.slab->L != L || (L == 1 && ctrl))  // (the slab SpMV takes no control word)
             return hipErrorInvalidValue;
         return L == 1 ? launch_slab(h, plan, d_X, d_Y) : launch_slab_mm(h, plan, d_X, d_Y, L, ld, ctrl);

@@ -1,7 +1,7 @@
 // mspmv_tri.hip -- triangular factors on the device: the IC(0) and ILU(0) factor objects of include/mspmv.h
 // (create, destroy, colours, one solve, the whole apply) and the level-scheduled sync-free solve of a
 // natural-order factor (k_trsv_tagged).  The colour sweeps of a multi-colour factor are mspmv_color.hip's.
-// The solvers (mspmv_api.hip, mspmv_cg_passes.hip, mspmv_bicgstab.hip) see a factor through tri_apply,
+// The solvers (mspmv_solve.hip, mspmv_cg_passes.hip, mspmv_bicgstab.hip) see a factor through tri_apply,
 // tri_workspace, ilu0_workspace and tri_graph_key (mspmv_internal.h) and never ask which kind it is.
 #include "mspmv_internal.h"
 #include "mspmv_device.h"

@@ -98,7 +98,7 @@ def check_kernel(g, name, L):
         assert g.plan_block_tiles(L) > 0
     elif name == "node_blocks":
         # 72 columns per row, and boundary nodes: at L = 1 the tile kernel stages the node blocks itself, the
-        # L-wide products keep their merge tiles (get_plan: k_spmm_blk needs every tile a register run tile)
+        # L-wide products keep their merge tiles (solver_plan: k_spmm_blk needs every tile a register run tile)
         assert k.startswith(f"k_spmm_tile<{L}," if L > 1 else "k_spmv_tile<"), k
         if L == 1:
             assert g.plan_block_tiles(1) > 0

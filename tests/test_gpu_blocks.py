@@ -383,7 +383,7 @@ def test_blocks_mixed_plan_spmm(orc, name, L):
 @pytest.mark.parametrize("runs", ["0", "1", "auto"])
 @pytest.mark.parametrize("name", ["regular", "perturbed_small", "perturbed_heavy"])
 def test_blocks_run_plan(orc, monkeypatch, name, runs):
-    """The run-balanced node-block plan (mspmv_api.hip spmv_runs_decide: tiles cut at run starts, <= 8
+    """The run-balanced node-block plan (mspmv_plan.hip spmv_runs_decide: tiles cut at run starts, <= 8
     run chunks each, so k_spmv_blk takes every tile in one round of its half-wave slots): automatic on
     every all-register node-block plan, off with MSPMV_SPMV_RUNS=0.  Parity against SpmvGold under the
     plan the product ran on, and the L = 16 node-block SpMM on it against OmpCsrSpmmT; bitwise repeats;

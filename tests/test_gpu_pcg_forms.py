@@ -13,13 +13,13 @@ Each case asserts its form from the plan queries before it is used, never skips 
                      at L = 8 (the form without the 6 is unreachable: see pcg_cases.py)
   node_blocks_mixed  plan_block_tiles(1) > 0 and num_carries > 0: the tile kernel staging node blocks, with carries
                      (L = 1), and the L = 8 merge tiles with carries
-The queries answer for the plain product's plan (get_plan(h, L, plain = true)); the solvers call get_plan(h, L)
-without that flag.  At L > 1 the two differ only by windows and slabs (and the run-balanced node-block plan, which
+The queries answer for the plain product's plan (product_plan(h, L)); the solvers call solver_plan(h, L).
+At L > 1 the two differ only by windows and slabs (and the run-balanced node-block plan, which
 is taken only where every tile of the solver's plan is a register run tile already); at L = 1 also by the one-wave
 plan, which the L = 1 cases rule out by asserting 256 lanes.
 
 This module is not among conftest's DEFAULT_PLAN_MODULES, so MSPMV_DIA=0 is set for it.  That changes nothing the
-solvers do: both PCGs call get_plan(h, L) and get_plan(hm, L) without the plain-product flag (cg_solve_native), which
+solvers do: both PCGs call solver_plan(h, L) and solver_plan(hm, L) (cg_solve_native), which
 never returns the offset windows or a column slab; it only keeps the handles of the stencil cases from taking
 windows for the plain products these tests interleave.
 
