@@ -391,17 +391,35 @@ ORC_EXPORT int orc_cg_single(int num_rows, const int *row_offsets, const int *co
 /* ------------------------------------------------------------------------- */
 /* Multi-RHS BLAS-1: work_2025/cg/utils_multiple.hpp:8-59 (interleaved n x L) */
 /* ------------------------------------------------------------------------- */
+/* The threads' partial sums (a static partition of the rows, as the reduction clause made them) are added in thread
+ * order: an OpenMP reduction combines them in whatever order the threads finish, so the same vectors gave sums that
+ * differed in their last bits from one call to the next -- and a frozen column's residual moved between iterations. */
 static void dot_multiple(int n, int L, const double *x, const double *y, double *result)
 {
-    for (int i = 0; i < L; i++)
-        result[i] = 0.0;
-#pragma omp parallel for reduction(+ : result[0 : L])
-    for (int j = 0; j < n; ++j) {
-        const double *xr = x + (size_t)j * L;
-        const double *yr = y + (size_t)j * L;
-        for (int i = 0; i < L; ++i)
-            result[i] += xr[i] * yr[i];
+    int team = omp_get_max_threads();
+    double *part = (double *)calloc((size_t)team * L, sizeof(double));
+    int used = 1;
+#pragma omp parallel num_threads(team)
+    {
+        const int t = omp_get_thread_num(), T = omp_get_num_threads();
+        const int lo = (int)((long long)n * t / T), hi = (int)((long long)n * (t + 1) / T);
+        double *mine = part + (size_t)t * L;
+        for (int j = lo; j < hi; ++j) {
+            const double *xr = x + (size_t)j * L;
+            const double *yr = y + (size_t)j * L;
+            for (int i = 0; i < L; ++i)
+                mine[i] += xr[i] * yr[i];
+        }
+        if (t == 0)
+            used = T;
     }
+    for (int i = 0; i < L; i++) {
+        double s = 0.0;
+        for (int t = 0; t < used; ++t)
+            s += part[(size_t)t * L + i];
+        result[i] = s;
+    }
+    free(part);
 }
 
 static void axpy_multiple(int n, int L, const double *a, const double *x, double *y)

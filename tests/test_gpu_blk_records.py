@@ -6,7 +6,10 @@ escapes to its row of the 16-bit column stream.  Products, sums and their order 
 on plans of register run tiles alone (kernel name ending ",6,false>") y is the pair tree of each row,
 restated in numpy here and required bit for bit: prod[k] = val[k] * x[col[k]] padded with +0.0 to 64,
 pair[l] = prod[2l] + prod[2l+1], then halves of 16, 8, 4, 2, 1.  Mixed plans are checked against the
-oracle under check_parity."""
+oracle under check_parity.
+
+test_record_boundary runs the boundary itself on the device -- rows of exactly 11, 12 and 13 column-runs, patterns 63
+and 64 columns wide, a pattern row that is not its run's first -- on generated FEM nodes (fem_nodes)."""
 import numpy as np
 import pytest
 
@@ -222,3 +225,103 @@ def test_wide_column_range(monkeypatch, orc):
             check_parity(a, y, orc.spmv_gold(a, x), x, plan, 1)
     assert info["kname"].startswith("k_spmv_blk<0,"), info["kname"]
     assert info["records"][0] > 0
+
+
+# ---- the record boundary: 11, 12 and 13 column-runs, 63 and 64 columns, a pattern row that is not the run's first ----
+R12_ODD = (3, 5) * 6                  # 48 columns in 12 runs; every run odd, so a lane's pair straddles every entry
+R13 = R12_ODD + (4,)                  # 52 columns in 13 runs: one more than a record holds
+BOUNDARY_SHAPES = {
+    # name: (run lengths per node, cycled over the nodes; columns each node's first row is short by)
+    "r11": ([(3, 5) * 5 + (3,)], 0),
+    "r12_odd": ([R12_ODD], 0),
+    "r12_ones_first": ([(1,) * 11 + (37,)], 0),
+    "r12_ones_last": ([(37,) + (1,) * 11], 0),
+    "r13": ([R13], 0),
+    "mixed": ([R12_ODD, R13], 0),
+    "w64": ([(5,) * 11 + (9,)], 0),
+    "w63": ([(5,) * 11 + (8,)], 0),
+    "short_first_r12_odd": ([R12_ODD], 5),
+    "short_first_r13": ([R13], 5),
+}
+ESCAPING = {"r13", "mixed", "short_first_r13"}
+
+
+def fem_nodes(run_lengths, short_first=0, nodes=700, n=6000, seed=0):
+    """nodes - 1 FEM nodes of 6 rows and a last one of 2, the rows of a node sharing one column list: runs of
+    consecutive columns of the lengths run_lengths[node % len(run_lengths)], separated by gaps of 1-3 columns, from a
+    random first column (never equal to the node before's, so the two nodes' rows never agree on a prefix and no
+    run of the plan joins them; the last node's list ends at column n - 1).  short_first > 0: each node's first row is the list less its last short_first columns, so the row that
+    holds the run's pattern is not the run's first.  n = 6,000 keeps every tile on 16-bit columns."""
+    rng = np.random.default_rng(seed)
+    ro, ci = [0], []
+    prev = -1
+    for node in range(nodes):
+        lens = run_lengths[node % len(run_lengths)]
+        gaps = rng.integers(1, 4, len(lens) - 1)
+        rel = np.concatenate([np.arange(ln) + off for ln, off in
+                              zip(lens, np.concatenate([[0], np.cumsum(np.asarray(lens[:-1]) + gaps)]))])
+        span = int(rel[-1]) + 1
+        start = n - span if node == nodes - 1 else int(rng.integers(0, n - span + 1))
+        if start == prev:
+            start = start - 1 if start > 0 else start + 1
+        prev = start
+        for r in range(6 if node < nodes - 1 else 2):
+            row = start + (rel[:-short_first] if short_first and r == 0 else rel)
+            ci.append(row)
+            ro.append(ro[-1] + row.size)
+    ci = np.concatenate(ci).astype(np.int32)
+    assert ci.min() >= 0 and ci.max() == n - 1
+    va = rng.uniform(-1, 1, ci.size)
+    return mspmv.CsrMatrix.from_arrays(n, np.asarray(ro, np.int32), ci, va)
+
+
+def boundary_matrix(name):
+    """The named boundary shape, its runs-per-row and widths asserted on the CPU (before any handle is made)."""
+    run_lengths, short = BOUNDARY_SHAPES[name]
+    a = fem_nodes(run_lengths, short_first=short, seed=sorted(BOUNDARY_SHAPES).index(name))
+    cr = column_runs_per_row(a)
+    lens = np.diff(a.row_offsets)
+    node = np.arange(a.num_rows) // 6
+    first = np.arange(a.num_rows) % 6 == 0
+    want_runs = np.array([len(run_lengths[k % len(run_lengths)]) for k in node])
+    want_len = np.array([sum(run_lengths[k % len(run_lengths)]) for k in node])
+    if short:  # the first row lacks its last 5 columns: of R12_ODD's and of R13's list that is one run fewer
+        assert np.array_equal(lens[first], want_len[first] - short) and np.array_equal(cr[first], want_runs[first] - 1)
+    else:
+        assert np.array_equal(lens[first], want_len[first]) and np.array_equal(cr[first], want_runs[first])
+    assert np.array_equal(lens[~first], want_len[~first]) and np.array_equal(cr[~first], want_runs[~first])
+    assert 32 <= lens.min() and lens.max() <= 64  # k_build_blocks: patterns >= 32 columns wide pay, <= 64 are one chunk
+    assert a.num_rows % 6 == 2  # the last node has 2 rows
+    assert a.column_indices[-1] == a.num_cols - 1
+    return a, cr
+
+
+@pytest.mark.parametrize("name,runs_env", [(k, None) for k in BOUNDARY_SHAPES] + [("mixed", "0"), ("r12_odd", "0")])
+def test_record_boundary(monkeypatch, orc, name, runs_env):
+    """Rows of exactly 11, 12 and 13 column-runs (a record holds 12: En = dword(4 + min(e + 1, 11)) reads the twelfth
+    entry as its own successor), pairs that straddle every entry boundary, single-column runs first and last,
+    patterns 64 and 63 columns wide (w63 and the others' last node end at column n - 1: the pair's lane with one
+    column left), compact and escaped records in one tile (mixed), and a pattern row that is not the run's first,
+    compact and escaped (pstart > 0) -- on the run-balanced plan and, for two shapes, on the merge-path plan
+    (MSPMV_SPMV_RUNS=0: tiles of more than one round)."""
+    a, cr = boundary_matrix(name)
+    assert (cr.max() > 12) == (name in ESCAPING), np.bincount(cr)
+    x, y, info = run_pair(a, 50, runs_env, monkeypatch)
+    kname = info["kname"]
+    compact, escaped = info["records"]
+    print(f"{name} runs={runs_env}: {kname}, {info['nb']} of {info['plan']['num_tiles']} tiles on node blocks, "
+          f"{info['rounds']} of two rounds, records (compact, escaped) ({compact}, {escaped}), "
+          f"runs per row {np.flatnonzero(np.bincount(cr)).tolist()}")
+    assert kname.startswith("k_spmv_blk<0,"), kname
+    if name in ESCAPING:
+        assert escaped > 0
+        if name == "r13":
+            assert compact == 0  # every chunk's pattern has 13 runs
+        if name == "mixed":
+            assert compact > 0
+    else:
+        assert compact > 0 and escaped == 0
+    assert compact + escaped == count_chunks(a, info["plan"]["bounds"])
+    if kname.endswith(",6,false>"):
+        assert_pair_tree(f"{name}-runs{runs_env}", a, x, y, info)
+    check_parity(a, y, orc.spmv_gold(a, x), x, info["plan"], 1)
