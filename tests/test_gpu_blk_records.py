@@ -150,18 +150,23 @@ def test_mixed_plan_records(monkeypatch, orc):
     assert compact > 0
 
 
-def test_fallback_tiles_beside_records(monkeypatch, orc):
-    """Shape 1 with 1,200 stencil rows (7 per row, no runs) below it: k_spmv_blk<.., true>, whose tiles
-    without runs have all-zero records (count 0) and take the register fallback."""
-    monkeypatch.delenv("MSPMV_SPMV_RUNS", raising=False)
+def fallback_matrix():
+    """Shape 1 with 1,200 stencil rows (7 per row, no runs) below it."""
     f = mspmv.CsrMatrix.synth_fem_blocked(4198, 222000, 6, 60, seed=5)
     rng = np.random.default_rng(9)
     ms = 1200
     base = rng.integers(0, f.num_cols - 40, ms)
     ci = (base[:, None] + np.arange(0, 35, 5)[None, :]).astype(np.int32).reshape(-1)
     ro = np.concatenate([f.row_offsets, f.row_offsets[-1] + np.arange(7, 7 * ms + 1, 7)]).astype(np.int32)
-    a = mspmv.CsrMatrix.from_arrays(f.num_cols, ro, np.concatenate([f.column_indices, ci]),
-                                    np.concatenate([f.values, rng.uniform(0.5, 1.5, 7 * ms)]))
+    return mspmv.CsrMatrix.from_arrays(f.num_cols, ro, np.concatenate([f.column_indices, ci]),
+                                       np.concatenate([f.values, rng.uniform(0.5, 1.5, 7 * ms)]))
+
+
+def test_fallback_tiles_beside_records(monkeypatch, orc):
+    """Shape 1 with 1,200 stencil rows (7 per row, no runs) below it: k_spmv_blk<.., true>, whose tiles
+    without runs have all-zero records (count 0) and take the register fallback."""
+    monkeypatch.delenv("MSPMV_SPMV_RUNS", raising=False)
+    a = fallback_matrix()
     x = np.random.default_rng(47).uniform(-1, 1, a.num_cols)
     with mspmv.GpuCsr(a) as g:
         plan = g.tile_plan(1)

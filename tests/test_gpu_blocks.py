@@ -127,8 +127,8 @@ def register_rows(a, plan):
     return mask
 
 
-def test_blocks_empty_rows(orc):
-    """Empty rows inside runs (an empty row is a prefix of any list: it joins the run)."""
+def kron9_emptied():
+    """kron_fem9(50, 40, 6) with rows 0, 1 of every 37 emptied, and the mask of the rows kept."""
     a = kron_fem9(50, 40, 6)
     ro = a.row_offsets.copy()
     keep = np.ones(a.num_rows, bool)
@@ -138,6 +138,12 @@ def test_blocks_empty_rows(orc):
     mask = np.repeat(keep, np.diff(ro))
     e = mspmv.CsrMatrix.from_arrays(a.num_cols, np.concatenate([[0], np.cumsum(lens)]).astype(np.int32),
                                     a.column_indices[mask], a.values[mask])
+    return e, keep
+
+
+def test_blocks_empty_rows(orc):
+    """Empty rows inside runs (an empty row is a prefix of any list: it joins the run)."""
+    e, keep = kron9_emptied()
     x = np.random.default_rng(3).uniform(-1, 1, e.num_cols)
     with mspmv.GpuCsr(e) as g:
         assert g.plan_block_tiles(1) > 0

@@ -217,27 +217,35 @@ def _mk(m, n, lens, seed=0):
     return mspmv.CsrMatrix(m, n, int(ro[-1]), ro, ci, rng.uniform(-1, 1, len(ci)))
 
 
-@pytest.mark.parametrize("case", ["all_empty", "one_long_row", "long_rows_many_tiles", "single_entry",
-                                  "leading_empty", "trailing_empty", "dense_rows", "one_row_matrix"])
-def test_edge_cases(orc, case):
+EDGE_CASES = ["all_empty", "one_long_row", "long_rows_many_tiles", "single_entry",
+              "leading_empty", "trailing_empty", "dense_rows", "one_row_matrix"]
+LONG_ROWS = (10, 1500, 2999)  # the hub rows of long_rows_many_tiles
+
+
+def edge_case(case):
     if case == "all_empty":
-        a = _mk(5000, 100, np.zeros(5000, int))
-    elif case == "one_long_row":
-        a = _mk(1, 200000, [150000])
-    elif case == "long_rows_many_tiles":
+        return _mk(5000, 100, np.zeros(5000, int))
+    if case == "one_long_row":
+        return _mk(1, 200000, [150000])
+    if case == "long_rows_many_tiles":
         lens = np.ones(3000, int)
-        lens[[10, 1500, 2999]] = [40000, 9000, 25000]
-        a = _mk(3000, 60000, lens)
-    elif case == "single_entry":
-        a = _mk(1, 1, [1])
-    elif case == "leading_empty":
-        a = _mk(9000, 500, np.r_[np.zeros(8000, int), np.full(1000, 7)])
-    elif case == "trailing_empty":
-        a = _mk(9000, 500, np.r_[np.full(1000, 7), np.zeros(8000, int)])
-    elif case == "dense_rows":
-        a = _mk(64, 4096, np.full(64, 4096))
-    else:
-        a = _mk(1, 10, [10])
+        lens[list(LONG_ROWS)] = [40000, 9000, 25000]
+        return _mk(3000, 60000, lens)
+    if case == "single_entry":
+        return _mk(1, 1, [1])
+    if case == "leading_empty":
+        return _mk(9000, 500, np.r_[np.zeros(8000, int), np.full(1000, 7)])
+    if case == "trailing_empty":
+        return _mk(9000, 500, np.r_[np.full(1000, 7), np.zeros(8000, int)])
+    if case == "dense_rows":
+        return _mk(64, 4096, np.full(64, 4096))
+    assert case == "one_row_matrix"
+    return _mk(1, 10, [10])
+
+
+@pytest.mark.parametrize("case", EDGE_CASES)
+def test_edge_cases(orc, case):
+    a = edge_case(case)
     x = np.random.default_rng(3).uniform(-1, 1, a.num_cols)
     with mspmv.GpuCsr(a) as g:
         y = g.spmv(x)
