@@ -459,6 +459,50 @@ MSPMV_API mspmv_status mspmv_plan_block_rounds(mspmv_handle h, int L, int *tiles
  * or, a pattern of more such runs, from its row of the 16-bit column stream (*chunks_escaped).  Both 0
  * for plans without node blocks. */
 MSPMV_API mspmv_status mspmv_plan_block_records(mspmv_handle h, int L, int *chunks_compact, int *chunks_escaped);
+/* Which layout forms the column-slab plan of the plain L-column product holds (L = 1: k_spmv_slab or
+ * k_spmv_sell; L = 8, 16: k_spmm_slab), counted on the host while the plan was built.  *on_slab = 0 and
+ * no counter written when that product runs on another plan.  stats[i], i < min(count,
+ * MSPMV_SLAB_STAT_COUNT), receives counter i; counters of another kernel's forms are 0. */
+enum mspmv_slab_stat {
+    /* every slab plan */
+    MSPMV_SLAB_STAT_BLOCKS = 0,
+    MSPMV_SLAB_STAT_GROUPS,            /* column groups (1: blocks hold whole rows' nonzeros) */
+    MSPMV_SLAB_STAT_UNITS,             /* chunks (k_spmv_slab, k_spmm_slab) or segments (k_spmv_sell) */
+    MSPMV_SLAB_STAT_UNITS_MAX,         /* ... the most in one block (the block's LDS table) */
+    MSPMV_SLAB_STAT_ROWS_MAX,          /* the most rows ending in one block */
+    MSPMV_SLAB_STAT_EMPTY_BLOCKS,      /* blocks without a nonzero (an empty column group) */
+    MSPMV_SLAB_STAT_CARRIES,           /* block boundaries a split row crosses */
+    /* k_spmv_slab and k_spmm_slab */
+    MSPMV_SLAB_STAT_CHUNKS_FULL,       /* chunks of exactly cfg.chunk nonzeros */
+    MSPMV_SLAB_STAT_CHUNKS_ENTRY_CUT,  /* chunks ended by their cfg.entries-th run */
+    MSPMV_SLAB_STAT_RUNS_CUT,          /* runs of one row cut by a chunk's end */
+    MSPMV_SLAB_STAT_CHUNKS_LONG,       /* chunks with runs summed by whole waves (SpMV) */
+    MSPMV_SLAB_STAT_LONG_RUNS_MAX,     /* ... the most such runs in one chunk */
+    MSPMV_SLAB_STAT_LG0,               /* chunks by lanes_log2 of their short runs: LG0 + lg, lg = 0..6 */
+    MSPMV_SLAB_STAT_SEGMENTS = MSPMV_SLAB_STAT_LG0 + 7, /* column segments (SpMM) */
+    MSPMV_SLAB_STAT_SEGMENTS_MAX,      /* ... the most in one block */
+    MSPMV_SLAB_STAT_SEGMENTS_FULL,     /* segments of exactly cfg.cols columns */
+    MSPMV_SLAB_STAT_SEGMENTS_RAGGED,   /* segments whose columns x L / 2 is no multiple of 64 (a partial DMA piece) */
+    /* k_spmv_sell: slices of short runs by form */
+    MSPMV_SLAB_STAT_PACK_8X1,          /* packed, K runs x slots: 8 x 1, 4 x 2, 2 x 3, 2 x 4 */
+    MSPMV_SLAB_STAT_PACK_4X2,
+    MSPMV_SLAB_STAT_PACK_2X3,
+    MSPMV_SLAB_STAT_PACK_2X4,
+    MSPMV_SLAB_STAT_PACK_1X5,          /* packed plans' slices of one run per lane: PACK_1X5 + slots - 5, slots = 5..8 */
+    MSPMV_SLAB_STAT_UNPACKED_1 = MSPMV_SLAB_STAT_PACK_1X5 + 4, /* unpacked: UNPACKED_1 + slots - 1, slots = 1..8 */
+    MSPMV_SLAB_STAT_MEDIUM_2 = MSPMV_SLAB_STAT_UNPACKED_1 + 8, /* medium slices: MEDIUM_2 + slots - 2, slots = 2..8 */
+    MSPMV_SLAB_STAT_SLICES_ODD = MSPMV_SLAB_STAT_MEDIUM_2 + 7, /* slices with an odd slot count (a lone last slot) */
+    MSPMV_SLAB_STAT_SLICES_PARTIAL,    /* slices holding fewer runs than they have places */
+    MSPMV_SLAB_STAT_LONG_1,            /* long runs of one piece, of two, of three or more */
+    MSPMV_SLAB_STAT_LONG_2,
+    MSPMV_SLAB_STAT_LONG_3PLUS,
+    MSPMV_SLAB_STAT_PIECES_MAX,        /* the most long-run pieces in one segment */
+    MSPMV_SLAB_STAT_SEGS_PIECES_ONLY,  /* segments with pieces and no slice */
+    MSPMV_SLAB_STAT_SEGS_REFILL,       /* segments of < 16 slices followed in their block by one of > 16 */
+    MSPMV_SLAB_STAT_PACKED_ROW_MAX,    /* the largest local row in a packed 16-bit run word */
+    MSPMV_SLAB_STAT_COUNT
+};
+MSPMV_API mspmv_status mspmv_slab_plan_stats(mspmv_handle h, int L, long long *stats, int count, int *on_slab);
 /* Host-only test hooks on the record's codec, no device needed.  Encode: a pattern of wc (0..64)
  * sorted distinct 16-bit column offsets into entries[12] (start | len << 16 | prefix << 24 per run of
  * consecutive columns, unused entries 0); *escaped = 1 and no entry when there are more than 12 runs.

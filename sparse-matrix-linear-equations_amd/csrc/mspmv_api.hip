@@ -1051,6 +1051,27 @@ mspmv_status mspmv_plan_block_records(mspmv_handle h, int L, int *chunks_compact
     return MSPMV_OK;
 }
 
+mspmv_status mspmv_slab_plan_stats(mspmv_handle h, int L, long long *stats, int count, int *on_slab)
+{
+    ST_TRY(check_handle(h));
+    if (!on_slab || (count > 0 && !stats))
+        return invalid("null out pointer");
+    if (!supported_L(L))
+        return (set_error("L must be one of 1, 2, 4, 8, 16"), MSPMV_ERR_UNSUPPORTED);
+    const TilePlan *plan = nullptr;
+    ST_TRY(product_plan(h, L, &plan));
+    *on_slab = plan->slab ? 1 : 0;
+    if (!plan->slab)
+        return MSPMV_OK;
+    SlabStats s = plan->slab->stats;
+    s.v[MSPMV_SLAB_STAT_BLOCKS] = plan->num_tiles;
+    s.v[MSPMV_SLAB_STAT_GROUPS] = plan->slab->groups;
+    s.v[MSPMV_SLAB_STAT_CARRIES] = plan->num_carries;
+    for (int i = 0; i < count && i < MSPMV_SLAB_STAT_COUNT; ++i)
+        stats[i] = s.v[i];
+    return MSPMV_OK;
+}
+
 mspmv_status mspmv_block_record_encode(const unsigned short *offsets, int wc, unsigned *entries, int *escaped)
 {
     if (!entries || !escaped || (wc > 0 && !offsets))

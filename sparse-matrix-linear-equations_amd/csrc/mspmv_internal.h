@@ -78,7 +78,27 @@ constexpr int kSellMaxSegs = 255;     // segments per block (their descriptors s
 // short runs packed per lane by the slice's longest run (<= 4): {runs per lane K, slots per run}
 constexpr int2 kSellPack[5] = {{1, 1}, {8, 1}, {4, 2}, {2, 3}, {2, 4}};
 constexpr int kSlabLongRun = 64;  // runs longer than this are summed by whole waves (listed first in a chunk)
+// Which layout forms a slab plan holds (mspmv_slab_plan_stats; indices: mspmv.h MSPMV_SLAB_STAT_*), counted
+// on the host while the plan is built: sums, except the *_MAX entries, which are maxima over blocks.
+struct SlabStats {
+    long long v[MSPMV_SLAB_STAT_COUNT] = {};
+    void add(int i, long long n = 1) { v[i] += n; }
+    void top(int i, long long n) { v[i] = n > v[i] ? n : v[i]; }
+    void merge(const SlabStats &o)
+    {
+        for (int i = 0; i < MSPMV_SLAB_STAT_COUNT; ++i) {
+            const bool is_max = i == MSPMV_SLAB_STAT_UNITS_MAX || i == MSPMV_SLAB_STAT_ROWS_MAX ||
+                                i == MSPMV_SLAB_STAT_LONG_RUNS_MAX || i == MSPMV_SLAB_STAT_SEGMENTS_MAX ||
+                                i == MSPMV_SLAB_STAT_PIECES_MAX || i == MSPMV_SLAB_STAT_PACKED_ROW_MAX;
+            if (is_max)
+                top(i, o.v[i]);
+            else
+                add(i, o.v[i]);
+        }
+    }
+};
 struct SlabData {
+    SlabStats stats;                    // the plan's forms (blocks, groups and carries are filled in when asked)
     int L = 1;                          // 1: the SpMV's plan (k_spmv_slab); 8 / 16: an SpMM plan (k_spmm_slab)
     int cfg = 0;                        // the kernel configuration the plan was cut for (SpMV: kSlabCfgs;
                                         // SpMM: slab_mm_cfg)

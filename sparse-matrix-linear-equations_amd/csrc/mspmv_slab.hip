@@ -654,6 +654,7 @@ struct SlabBlockOut {
     std::vector<int4> chunks;  // entry0 relative to the block
     std::vector<uint2> ents;
     int slabs = 0;
+    SlabStats st;
 };
 
 static void slab_block(const std::vector<int> &ro, const std::vector<int> &ci, const std::vector<double> &va,
@@ -708,13 +709,17 @@ static void slab_block(const std::vector<int> &ro, const std::vector<int> &ci, c
                 int k = q;
                 while (k < qe && k - start < C.chunk && row[(size_t)k] == row[(size_t)q])
                     ++k;
-                if (ne == C.entries)
+                if (ne == C.entries) {
+                    out.st.add(MSPMV_SLAB_STAT_CHUNKS_ENTRY_CUT);
                     break;
+                }
                 out.ents.push_back(make_uint2((unsigned)(q - start) | ((unsigned)(k - q) << 16), (unsigned)row[(size_t)q]));
+                out.st.add(MSPMV_SLAB_STAT_RUNS_CUT, k < qe && row[(size_t)k] == row[(size_t)q]);
                 ++ne;
                 q = k;
             }
             const int len = q - start;
+            out.st.add(MSPMV_SLAB_STAT_CHUNKS_FULL, len == C.chunk);
             // runs longer than kSlabLongRun first (whole waves sum them), then the short ones
             std::stable_partition(out.ents.begin() + e0, out.ents.end(),
                                   [](const uint2 &e) { return (int)(e.x >> 16) > kSlabLongRun; });
@@ -738,6 +743,9 @@ static void slab_block(const std::vector<int> &ro, const std::vector<int> &ci, c
                     lg = l;
                 }
             }
+            out.st.add(MSPMV_SLAB_STAT_CHUNKS_LONG, nlong > 0);
+            out.st.top(MSPMV_SLAB_STAT_LONG_RUNS_MAX, nlong);
+            out.st.add(MSPMV_SLAB_STAT_LG0 + lg);
             out.chunks.push_back(make_int4(base + start, len | (lg << 13) | (nlong << 16), smin + s, e0));
         }
     }
@@ -851,6 +859,14 @@ static mspmv_status slab_finish(mspmv_handle_s *h, TilePlan &p, int cfg, int gro
     }
     chunks.push_back(make_int4(0, 0, 0, (int)ents.size()));  // sentinel: the last chunk's entry end
     SlabData *s = new SlabData();
+    for (int t = 0; t < T; ++t) {
+        const SlabBlockOut &o = outs[(size_t)t];
+        s->stats.merge(o.st);
+        s->stats.add(MSPMV_SLAB_STAT_UNITS, (long long)o.chunks.size());
+        s->stats.top(MSPMV_SLAB_STAT_UNITS_MAX, (long long)o.chunks.size());
+        s->stats.top(MSPMV_SLAB_STAT_ROWS_MAX, dblk[(size_t)t].y);
+        s->stats.add(MSPMV_SLAB_STAT_EMPTY_BLOCKS, o.chunks.empty());
+    }
     s->cfg = cfg;
     s->groups = groups;
     s->num_chunks = (int)chunks.size() - 1;
@@ -908,6 +924,7 @@ struct SellBlockOut {
     std::vector<unsigned short> col;
     long long staged = 0;
     bool too_many = false;  // a segment with more long-run pieces than the kernel's LDS table holds
+    SlabStats st;
 };
 
 static void sell_block(const std::vector<int> &ro, const std::vector<int> &ci, const std::vector<double> &va, int r0,
@@ -977,6 +994,7 @@ static void sell_block(const std::vector<int> &ro, const std::vector<int> &ci, c
                 for (int j = 0; j < r.len; ++j)
                     put_val(base + j, r.first + j);
                 const int np = (r.len + 511) / 512, first = (int)o.longs.size() - long0;
+                o.st.add(np == 1 ? MSPMV_SLAB_STAT_LONG_1 : np == 2 ? MSPMV_SLAB_STAT_LONG_2 : MSPMV_SLAB_STAT_LONG_3PLUS);
                 for (int q = 0; q < np; ++q)
                     o.longs.push_back(make_int4((int)base + 512 * q, std::min(512, r.len - 512 * q), r.row,
                                                 first | (np << 16)));
@@ -986,6 +1004,7 @@ static void sell_block(const std::vector<int> &ro, const std::vector<int> &ci, c
         }
         if ((int)o.longs.size() - long0 > kSellMaxPieces)
             o.too_many = true;
+        o.st.top(MSPMV_SLAB_STAT_PIECES_MAX, (long long)o.longs.size() - long0);
         std::stable_sort(shorts.begin(), shorts.end(), [](const Run &x, const Run &y) { return x.len > y.len; });
         for (size_t i0 = 0; i0 < shorts.size();) {
             const int Lmax = shorts[i0].len;
@@ -1005,12 +1024,20 @@ static void sell_block(const std::vector<int> &ro, const std::vector<int> &ci, c
                 for (int j = 0; j < r.len; ++j)
                     put_val(slot_at(base, S, k * stride + j, i), r.first + j);
                 if (pack) {
+                    o.st.top(MSPMV_SLAB_STAT_PACKED_ROW_MAX, r.row);
                     o.sents[(size_t)e0 + (size_t)i * K + k] = (unsigned short)(r.row | (r.len << 12));
                 } else {  // {row, length}, as the medium runs' words
                     o.sents[(size_t)e0 + 2 * (size_t)i] = (unsigned short)r.row;
                     o.sents[(size_t)e0 + 2 * (size_t)i + 1] = (unsigned short)r.len;
                 }
             }
+            o.st.add(!pack  ? MSPMV_SLAB_STAT_UNPACKED_1 + S - 1
+                     : K == 8 ? MSPMV_SLAB_STAT_PACK_8X1
+                     : K == 4 ? MSPMV_SLAB_STAT_PACK_4X2
+                     : K == 2 ? (stride == 3 ? MSPMV_SLAB_STAT_PACK_2X3 : MSPMV_SLAB_STAT_PACK_2X4)
+                              : MSPMV_SLAB_STAT_PACK_1X5 + S - 5);
+            o.st.add(MSPMV_SLAB_STAT_SLICES_ODD, S & 1);
+            o.st.add(MSPMV_SLAB_STAT_SLICES_PARTIAL, n < 64 * K);
             o.slices.push_back(make_int4((int)base, S, e0, K));
             i0 += (size_t)n;
         }
@@ -1033,7 +1060,16 @@ static void sell_block(const std::vector<int> &ro, const std::vector<int> &ci, c
                 o.sents.push_back(r ? (unsigned short)r->row : (unsigned short)0);
                 o.sents.push_back(r ? (unsigned short)r->len : (unsigned short)0);
             }
+            o.st.add(MSPMV_SLAB_STAT_MEDIUM_2 + Lm - 2);
+            o.st.add(MSPMV_SLAB_STAT_SLICES_ODD, Lm & 1);
+            o.st.add(MSPMV_SLAB_STAT_SLICES_PARTIAL, n < 8);
             o.slices.push_back(make_int4((int)base, Lm | (1 << 16), e0, 1));
+        }
+        const int nsl = (int)o.slices.size() - slice0;
+        o.st.add(MSPMV_SLAB_STAT_SEGS_PIECES_ONLY, nsl == 0 && (int)o.longs.size() > long0);
+        if (!o.segs.empty()) {
+            const int4 &prev = o.segs.back();
+            o.st.add(MSPMV_SLAB_STAT_SEGS_REFILL, prev.z - prev.y < 16 && nsl > 16);
         }
         o.segs.push_back(make_int4(base, slice0, (int)o.slices.size(), long0));
         o.staged += (long long)W * 8;
@@ -1091,6 +1127,14 @@ static mspmv_status sell_finish(mspmv_handle_s *h, TilePlan &p, const std::vecto
     s->num_chunks = (int)segs.size() - 1;
     s->num_entries = (int)longs.size();
     s->x_bytes_per_nnz = (double)staged / (double)h->nnz;
+    for (int t = 0; t < T; ++t) {
+        const SellBlockOut &o = outs[(size_t)t];
+        s->stats.merge(o.st);
+        s->stats.add(MSPMV_SLAB_STAT_UNITS, (long long)o.segs.size());
+        s->stats.top(MSPMV_SLAB_STAT_UNITS_MAX, (long long)o.segs.size());
+        s->stats.top(MSPMV_SLAB_STAT_ROWS_MAX, blk[(size_t)t].y);
+        s->stats.add(MSPMV_SLAB_STAT_EMPTY_BLOCKS, o.segs.empty());
+    }
     p.slab = s;
     mspmv_status st;
     if ((st = slab_upload(&s->d_blk, blk)) != MSPMV_OK || (st = slab_upload(&s->d_chunk, segs)) != MSPMV_OK ||
@@ -1335,13 +1379,12 @@ constexpr SlabMmCfg kSlabMmCfgs[] = {
 constexpr int kSlabMmNumCfgs = (int)(sizeof(kSlabMmCfgs) / sizeof(kSlabMmCfgs[0]));
 constexpr int kSlabMmSets = 4;  // stream chunks in flight per block (register sets)
 
-static int slab_mm_lab_cfg()  // lab: MSPMV_SPMM_SLAB_CFG picks a configuration by index (A/B runs)
+// lab: MSPMV_SPMM_SLAB_CFG picks a configuration by index (A/B runs); read at each handle's decision, as
+// MSPMV_SPMV_SLAB is (tests set it per matrix)
+static int slab_mm_lab_cfg()
 {
-    static const int v = [] {
-        const char *e = getenv("MSPMV_SPMM_SLAB_CFG");
-        return e && *e ? atoi(e) : -1;
-    }();
-    return v;
+    const char *e = getenv("MSPMV_SPMM_SLAB_CFG");
+    return e && *e ? atoi(e) : -1;
 }
 
 const SlabMmCfg &slab_mm_cfg(int L, int which)
@@ -1649,6 +1692,7 @@ struct SlabMmBlockOut {
     std::vector<uint2> ents;
     long long staged_cols = 0;
     bool ok = true;
+    SlabStats st;
 };
 
 static void slab_mm_block(const SlabMmCfg &cfg, const std::vector<int> &ro, const std::vector<int> &ci,
@@ -1669,10 +1713,14 @@ static void slab_mm_block(const SlabMmCfg &cfg, const std::vector<int> &ro, cons
             ++k;
         seg_lo.push_back(lo);
         seg_n.push_back(u[k - 1] - lo + 1);
+        out.st.add(MSPMV_SLAB_STAT_SEGMENTS_FULL, seg_n.back() == cfg.cols);
+        out.st.add(MSPMV_SLAB_STAT_SEGMENTS_RAGGED, seg_n.back() * (cfg.L / 2) % 64 != 0);
         out.staged_cols += u[k - 1] - lo + 1;
         i = k;
     }
     const int ns = (int)seg_lo.size();
+    out.st.add(MSPMV_SLAB_STAT_SEGMENTS, ns);
+    out.st.top(MSPMV_SLAB_STAT_SEGMENTS_MAX, ns);
     auto seg_of = [&](int c) { return (int)(std::upper_bound(seg_lo.begin(), seg_lo.end(), c) - seg_lo.begin()) - 1; };
     std::vector<int> off((size_t)ns + 1, 0);
     for (int k = n0; k < n1; ++k)
@@ -1708,10 +1756,13 @@ static void slab_mm_block(const SlabMmCfg &cfg, const std::vector<int> &ro, cons
                 while (k < qe && k - start < cfg.chunk && row[(size_t)k] == row[(size_t)q])
                     ++k;
                 out.ents.push_back(make_uint2((unsigned)(q - start) | ((unsigned)(k - q) << 16), (unsigned)row[(size_t)q]));
+                out.st.add(MSPMV_SLAB_STAT_RUNS_CUT, k < qe && row[(size_t)k] == row[(size_t)q]);
                 ++ne;
                 q = k;
             }
             const int len = q - start;
+            out.st.add(MSPMV_SLAB_STAT_CHUNKS_FULL, len == cfg.chunk);
+            out.st.add(MSPMV_SLAB_STAT_CHUNKS_ENTRY_CUT, ne == cfg.entries && q < qe && len < cfg.chunk);
             // nonzero lanes per run: the fewest latency steps -- rounds of runs over the block's groups
             // x (the run's products per lane + its butterfly + ~8 steps of LDS round trips)
             const int mean = (len + ne - 1) / ne;
@@ -1725,6 +1776,7 @@ static void slab_mm_block(const SlabMmCfg &cfg, const std::vector<int> &ro, cons
                     lg = l;
                 }
             }
+            out.st.add(MSPMV_SLAB_STAT_LG0 + lg);
             out.chunks.push_back(make_int4(start, len | (lg << 13) | (seg_n[(size_t)s] << 16), seg_lo[(size_t)s], e0));
         }
     }
@@ -1784,6 +1836,14 @@ mspmv_status build_slab_mm_plan(mspmv_handle_s *h, int L, TilePlan &p)
     s->num_chunks = (int)chunks.size() - 1;
     s->num_entries = (int)ents.size();
     s->x_bytes_per_nnz = (double)staged * 8.0 * L / (double)h->nnz;
+    for (int t = 0; t < T; ++t) {
+        const SlabMmBlockOut &o = outs[(size_t)t];
+        s->stats.merge(o.st);
+        s->stats.add(MSPMV_SLAB_STAT_UNITS, (long long)o.chunks.size());
+        s->stats.top(MSPMV_SLAB_STAT_UNITS_MAX, (long long)o.chunks.size());
+        s->stats.top(MSPMV_SLAB_STAT_ROWS_MAX, blk[(size_t)t].y);
+        s->stats.add(MSPMV_SLAB_STAT_EMPTY_BLOCKS, o.chunks.empty());
+    }
     p.slab = s;
     if ((st = slab_upload(&s->d_blk, blk)) != MSPMV_OK || (st = slab_upload(&s->d_chunk, chunks)) != MSPMV_OK ||
         (st = slab_upload(&s->d_ent, ents)) != MSPMV_OK || (st = slab_upload(&s->d_val, oval, kNnzPad)) != MSPMV_OK ||

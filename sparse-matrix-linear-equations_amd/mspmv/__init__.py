@@ -44,6 +44,21 @@ SUPPORTED_L = (1, 2, 4, 8, 16)  # native tile-kernel widths; SpMM and the CGs ta
 # (column chunks / groups of these widths; the sharded CG and the timing helpers native only)
 
 
+# mspmv_slab_plan_stats' counters, in the order of mspmv.h's MSPMV_SLAB_STAT_* (lower case, prefix dropped;
+# the ranged ones spelt out: lg0..lg6, pack_1x5..8, unpacked_1..8, medium_2..8)
+SLAB_STATS = (
+    ["blocks", "groups", "units", "units_max", "rows_max", "empty_blocks", "carries", "chunks_full",
+     "chunks_entry_cut", "runs_cut", "chunks_long", "long_runs_max"]
+    + [f"lg{i}" for i in range(7)]
+    + ["segments", "segments_max", "segments_full", "segments_ragged", "pack_8x1", "pack_4x2", "pack_2x3", "pack_2x4"]
+    + [f"pack_1x{i}" for i in range(5, 9)]
+    + [f"unpacked_{i}" for i in range(1, 9)]
+    + [f"medium_{i}" for i in range(2, 9)]
+    + ["slices_odd", "slices_partial", "long_1", "long_2", "long_3plus", "pieces_max", "segs_pieces_only",
+       "segs_refill", "packed_row_max"]
+)
+
+
 class MspmvError(RuntimeError):
     def __init__(self, status: int, where: str, msg: str):
         super().__init__(f"{where}: {STATUS.get(status, status)}: {msg}")
@@ -138,6 +153,7 @@ _SIGS = {
     "mspmv_plan_block_tiles": (_I, [_P, _I, _PI]),
     "mspmv_plan_block_rounds": (_I, [_P, _I, _PI]),
     "mspmv_plan_block_records": (_I, [_P, _I, _PI, _PI]),
+    "mspmv_slab_plan_stats": (_I, [_P, _I, _P, _I, _PI]),
     "mspmv_block_record_encode": (_I, [_P, _I, _P, _PI]),
     "mspmv_block_record_decode": (_I, [_P, _I, ctypes.POINTER(ctypes.c_uint)]),
     "mspmv_tile_modes": (_I, [_P, _I, _P]),
@@ -592,6 +608,14 @@ class GpuCsr:
         c, e = ctypes.c_int(), ctypes.c_int()
         _check(lib.mspmv_plan_block_records(self.h, L, ctypes.byref(c), ctypes.byref(e)), "plan_block_records")
         return c.value, e.value
+
+    def slab_plan_stats(self, L: int = 1):
+        """The forms the L-wide product's column-slab plan holds, {SLAB_STATS name: count}
+        (mspmv_slab_plan_stats), or None when that product is not on a slab plan."""
+        out = np.zeros(len(SLAB_STATS), np.int64)
+        on = ctypes.c_int()
+        _check(lib.mspmv_slab_plan_stats(self.h, L, _ptr(out), out.size, ctypes.byref(on)), "slab_plan_stats")
+        return dict(zip(SLAB_STATS, (int(v) for v in out))) if on.value else None
 
     def spmv(self, x: np.ndarray) -> np.ndarray:
         x = np.ascontiguousarray(x, np.float64)

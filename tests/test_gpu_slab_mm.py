@@ -55,6 +55,12 @@ def test_slab_mm_parity(orc, slab_mm_on, name, L):
     with mspmv.GpuCsr(a) as g:
         Y = g.spmm(X)
         kname = g.spmm_kernel_name(L)
+        st = g.slab_plan_stats(L)
+        # which kernel the case ran, in the test's output: a MAY_DECLINE case on the tiles tests nothing of k_spmm_slab
+        # (test_gpu_slab_edges.py holds the cases that may not decline: split rows, table limits, every configuration)
+        print(f"slab_mm {name} L={L}: {kname}" + (f", most chunks in a block {st['units_max']} of 127, carries "
+                                                   f"{st['carries']}" if st else ", slab plan declined"))
+        assert (st is not None) == kname.startswith("k_spmm_slab<")
         if name not in MAY_DECLINE:
             assert kname.startswith("k_spmm_slab<"), kname
         plan = g.tile_plan(L)
