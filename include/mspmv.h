@@ -207,6 +207,44 @@ MSPMV_API mspmv_status mspmv_dbicgstab_multi_dev(mspmv_handle h, const double *d
                                                  int max_iters, double tolerance, int *iters, double *max_err_hist,
                                                  int hist_cap);
 
+/* ---- block CG (SPD systems, one Krylov space for all right-hand sides) ------------------ */
+/* Block conjugate gradient in Dubrulle's BCGrQ form of O'Leary's method, for a symmetric positive
+ * definite matrix.  Unlike every other multi-RHS solver here -- L lock-step recurrences that share
+ * the matrix read and nothing else -- the L columns share ONE Krylov space: each iterate minimises
+ * over the sum of the columns' spaces, so the iteration count falls as L grows -- by much where the
+ * system is small or has few slow modes against L, by little on large smooth ones, while an
+ * iteration costs more than the lock-step CG's (measured: DESIGN.md 4.4d).  No reference
+ * counterpart (its CGSolveMultiple is the lock-step form).  With the interleaved n x L panels as
+ * matrices, all small matrices L x L, and chol(G) the upper factor zeta with G = zeta^T zeta:
+ *     init:  X = 0;  H = B^T B;  zeta = chol(H);  C = zeta;  W = B zeta^-1;  S = W;
+ *            bnorm_j = ||C e_j||_2 (= ||B_j||; 0 -> 1)
+ *     iter:  Q = A S
+ *            G = S^T Q;  xi = G^-1 (by chol(G));  T = xi C
+ *            X += S T;  V = W - Q xi;  H = V^T V
+ *            zeta = chol(H);  C <- zeta C;  rel_j = ||C e_j||_2 / bnorm_j
+ *            history[k] = max_j rel_j;  stop when every rel_j < tolerance, counting this iteration
+ *            W = V zeta^-1;  S = W + S zeta^T
+ * W is an orthonormal basis of the residual block R = W C, so ||R e_j|| = ||C e_j|| and columns that
+ * converge at different speeds do not drive G or H singular.  An iteration is one product and three
+ * streaming passes; the two Gram matrices fold in a fixed order, so a solve repeats bit for bit.
+ * max_err_hist (optional) receives the per-iteration max over the columns of rel_j, as
+ * mspmv_dcg_multi's; *iters the iterations completed (an iteration is complete once X and the
+ * residual norms are updated).  The columns are coupled: there are no per-column masks and no
+ * per-column freeze, and breakdown is one rule -- a Cholesky pivot of H or G that is <= 0 or
+ * non-finite (a zero or linearly dependent right-hand-side column at the init; an exactly converged
+ * direction later) ends the solve with MSPMV_ERR_BREAKDOWN.  X then holds the iterate of the last
+ * completed iteration (0 when the init broke, *iters = 0), and the error text names the matrix, the
+ * pivot index and the iteration: solve such a block with mspmv_dcg_multi, whose columns are
+ * independent (deflation is not implemented).  L must be 1, 2, 4, 8 or 16: column groups would
+ * uncouple the block, so any other width is MSPMV_ERR_UNSUPPORTED.  MSPMV_ERR_INVALID for a
+ * non-square matrix, max_iters < 0, null vectors, or device vectors not 16-byte aligned.
+ * mspmv_cg_kernel_name then reads "BlockCG-rQ (1 SpMM + 3 passes)", and
+ * mspmv_solver_product_kernel_name names the product's kernel as for BiCGSTAB. */
+MSPMV_API mspmv_status mspmv_dbcg_multi(mspmv_handle h, const double *B, double *X, int L, int max_iters,
+                                        double tolerance, int *iters, double *max_err_hist, int hist_cap);
+MSPMV_API mspmv_status mspmv_dbcg_multi_dev(mspmv_handle h, const double *d_B, double *d_X, int L, int max_iters,
+                                            double tolerance, int *iters, double *max_err_hist, int hist_cap);
+
 /* ---- SPAI-preconditioned block CG ---------------------------------------------------- */
 /* SPAI preconditioner M with A's own pattern, SparseApproximateInversion
  * (work_2025/cg/sparse_approximate_inversion.hpp:40-321): column k of M minimises
@@ -570,6 +608,12 @@ MSPMV_API const char *mspmv_cg_kernel_name(mspmv_handle h);
  * sliced-ELL or run-balanced plans.  For a width outside 1, 2, 4, 8, 16 it names the last column group's kernel.
  * "" before any such solve.  Read-only: it changes no launch.  Valid until the next solve on the handle. */
 MSPMV_API const char *mspmv_solver_product_kernel_name(mspmv_handle h);
+/* The launch shape of the streaming solver passes (the split CG's, BiCGSTAB's, the block CG's) for panels of native
+ * width L on this handle: *pass_blocks = workgroups per pass (their folds run one level per factor of 32 blocks; the
+ * count depends on rows x L alone, never on a CU limit), *batch_iters = iterations per batch, which is also the
+ * length of the cached iteration graph (a solve of fewer iterations runs ungraphed).  Either may be null.
+ * Read-only: it changes no launch. */
+MSPMV_API mspmv_status mspmv_solver_pass_shape(mspmv_handle h, int L, int *pass_blocks, int *batch_iters);
 
 /* ---- fault detection ----------------------------------------------------------------- */
 /* The kernels' cross-workgroup folds (CG dot products, rows split between tiles, column groups) are

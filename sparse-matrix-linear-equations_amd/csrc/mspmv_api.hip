@@ -297,6 +297,7 @@ mspmv_status mspmv_destroy(mspmv_handle h)
     dev_free(h->d_partials_b);
     dev_free(h->d_gtickets);
     dev_free(h->d_scal);
+    dev_free(h->d_bcg);
     dev_free(h->d_red);
     dev_free(h->d_conv);
     dev_free(h->d_ctrl);
@@ -305,6 +306,7 @@ mspmv_status mspmv_destroy(mspmv_handle h)
     h->cg_graph.reset();
     h->bicg_graph.reset();
     h->pbicg_graph.reset();
+    h->bcg_graph.reset();
     if (h->d_flush)
         (void)hipFree(h->d_flush);
     if (h->h_ctrl)
@@ -389,6 +391,7 @@ mspmv_status mspmv_set_cu_limit(mspmv_handle h, int num_cus)
     h->cg_graph.reset();
     h->bicg_graph.reset();
     h->pbicg_graph.reset();
+    h->bcg_graph.reset();
     if (h->own_stream)
         (void)hipStreamDestroy(h->stream);
     h->stream = s;

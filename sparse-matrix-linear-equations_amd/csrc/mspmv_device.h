@@ -211,7 +211,7 @@ __device__ __forceinline__ bool take_ticket(unsigned *tk, int gsize, CgControl *
     return false;
 }
 
-// ---- the streaming solver passes' folds (mspmv_cg_passes.hip, mspmv_bicgstab.hip) ----
+// ---- the streaming solver passes' folds (mspmv_cg_passes.hip, mspmv_bicgstab.hip, mspmv_blockcg.hip) ----
 // Deterministic multi-level "last block done" reduction of per-slot column partials.  The
 // caller has stored partials[slot][0..L) (agent scope, vmcnt drained) and synchronised.  Slots
 // form groups of kSlotGroup; the last of a group to arrive (one agent-scope ticket per group)

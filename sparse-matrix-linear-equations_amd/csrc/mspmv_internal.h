@@ -320,6 +320,9 @@ struct mspmv_handle_s {
     unsigned *d_gtickets = nullptr;  // reduce_slots group tickets (zeroed once, self-resetting)
     size_t gtickets_cap = 0;
     mspmv::CgScalars *d_scal = nullptr;
+    // block CG (mspmv_blockcg.hip): the L x L matrices C, T, xi, zeta^-1, zeta^T and bnorm[L], written by the folds'
+    // last blocks (kBcgSmallDoubles; allocated by that solver only)
+    double *d_bcg = nullptr;
     double *d_red = nullptr;  // [L] p.Ap of the split multi-RHS iteration (k_spmm_tile MODE 2 -> k_cg_update)
     unsigned char *d_conv = nullptr;   // per-column converged flags
     mspmv::CgControl *d_ctrl = nullptr;
@@ -340,8 +343,9 @@ struct mspmv_handle_s {
     unsigned poison_value = 0;
     int poison_flags = 0;  // 0: none pending; MSPMV_POISON_* bits
     // CG's iteration graph; BiCGSTAB's (bicgstab_solve_native), cached apart so neither solver evicts the
-    // other's; and the ILU(0)-preconditioned BiCGSTAB's: the same workspace, other launches
-    mspmv::GraphCache cg_graph, bicg_graph, pbicg_graph;
+    // other's; the ILU(0)-preconditioned BiCGSTAB's; and the block CG's (bcg_solve_native): the same workspace,
+    // other launches
+    mspmv::GraphCache cg_graph, bicg_graph, pbicg_graph, bcg_graph;
     // timing
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double last_tile_kernel_ms = 0.0;
@@ -710,6 +714,17 @@ hipError_t launch_bicgstab_iteration(mspmv_handle_s *h, const TilePlan &plan, co
 // Shat = U^-1 L^-1 s before the second (both in ilu->d_hat, through ilu->d_y), X advanced along them.
 hipError_t launch_pbicgstab_iteration(mspmv_handle_s *h, mspmv_ilu0_s *ilu, const TilePlan &plan,
                                       const TilePlan *splan, double *d_x, int L, int nblk, double tol);
+// Block CG (mspmv_blockcg.hip, BCGrQ): init (k_bcg_init: X = 0, W = B, H = B^T B and its factor; k_bcg_dir in its
+// first form: W = B zeta^-1, S = W) and one iteration -- Q = A S, the G = S^T Q pass, the step pass (X, V, H = V^T V,
+// stop test), the direction pass.  W, S, Q live in h->d_r, d_p0, d_ap, the small matrices in h->d_bcg
+// (kBcgSmallDoubles).  Partial rows are L^2 wide.  A Cholesky pivot failure leaves kBcgBroke | (kBcgBrokeG: of G,
+// else of H) | pivot index in ctrl->breakdown.
+constexpr int kBcgSmallDoubles = 5 * 16 * 16 + 16;
+constexpr int kBcgBroke = 0x100;
+constexpr int kBcgBrokeG = 0x10;
+hipError_t launch_bcg_init(mspmv_handle_s *h, const double *d_b, double *d_x, int L, double tol, int nblk);
+hipError_t launch_bcg_iteration(mspmv_handle_s *h, const TilePlan &plan, const TilePlan *splan, double *d_x, int L,
+                                int nblk, double tol);
 // Iterations per CG batch / graph replay for an m-row, nnz-nonzero matrix and L columns.
 int cg_batch_iters(long long m, long long nnz, int L);
 // Pipelined single-RHS CG (L == 1 unless MSPMV_CG_SPLIT=1): init (x = 0, r = p0 = b, b.b

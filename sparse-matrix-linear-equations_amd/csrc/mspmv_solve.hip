@@ -1,7 +1,8 @@
-// mspmv_solve.hip -- the solver drivers behind the C-ABI's CG and BiCGSTAB entry points: the handle's workspace,
-// the protocol every batched solve follows (prologue, cached iteration graph, pipelined batches, collection), the
-// native-width solvers, column groups for any other width, and the host-pointer forms.  The iterations' kernels
-// are in mspmv_cg_passes.hip, mspmv_cg_resident.hip and mspmv_bicgstab.hip, the factors in mspmv_tri.hip.
+// mspmv_solve.hip -- the solver drivers behind the C-ABI's CG, BiCGSTAB and block CG entry points: the handle's
+// workspace, the protocol every batched solve follows (prologue, cached iteration graph, pipelined batches,
+// collection), the native-width solvers, column groups for any other width, and the host-pointer forms.  The
+// iterations' kernels are in mspmv_cg_passes.hip, mspmv_cg_resident.hip, mspmv_bicgstab.hip and mspmv_blockcg.hip,
+// the factors in mspmv_tri.hip.
 #include "mspmv_internal.h"
 
 #include <algorithm>
@@ -14,7 +15,8 @@
 using namespace mspmv;
 
 // ---- the workspace -------------------------------------------------------------------------
-// fold_width: columns of a partial row when wider than L (BiCGSTAB's two-dot folds: 2 L)
+// fold_width: columns of a partial row when wider than L (BiCGSTAB's two-dot folds: 2 L; the block CG's Gram
+// folds: L^2)
 static mspmv_status ensure_cg_workspace(mspmv_handle_s *h, int L, int nblk, int num_tiles, int hist_cap,
                                         int fold_width = 0)
 {
@@ -661,6 +663,80 @@ static mspmv_status bicgstab_solve_dev(mspmv_handle_s *h, const double *d_b, dou
         "were solved)");
 }
 
+// Block CG (BCGrQ, mspmv_blockcg.hip) on a panel of native width, by bicgstab_solve_native's protocol and plan
+// choice: one product per iteration on the plan the handle's plain L-wide product takes (offset windows, column
+// slabs), else on the merge tiles; the iteration graph cached under the solver's own exec and key.  The columns
+// share one Krylov space, so there are no column groups: any other width is MSPMV_ERR_UNSUPPORTED.
+static mspmv_status bcg_solve_native(mspmv_handle_s *h, const double *d_b, double *d_x, int L, int max_iters,
+                                     double tol, int *iters, double *hist, int hist_cap)
+{
+    if (h->m != h->n)
+        return invalid("block CG needs a square matrix");
+    if (!supported_L(L))
+        return (set_error("block CG: L must be one of 1, 2, 4, 8, 16 (the columns are coupled: no column groups)"),
+                MSPMV_ERR_UNSUPPORTED);
+    if (max_iters < 0)
+        return invalid("max_iters < 0");
+    if (h->m > 0 && (!d_b || !d_x))
+        return invalid("null vector");
+    if (!aligned16(d_b) || !aligned16(d_x))
+        return invalid("block CG vectors must be 16-byte aligned");
+    if (iters)
+        *iters = 0;
+    if (h->m == 0)
+        return MSPMV_OK;
+    const TilePlan *plan = nullptr, *splan = nullptr;
+    ST_TRY(product_plan(h, L, &splan));
+    if (!(splan->dia || (splan->slab && L > 1)))
+        splan = nullptr;
+    ST_TRY(solver_plan(h, L, &plan));
+    const int nblk = cg_update_blocks((long long)h->m * L, h->num_cus);
+    const int cap = hist ? std::max(hist_cap, 0) : 0;
+    // partial rows of the Gram folds are L^2 wide, one per block of the passes: the products take no partials
+    ST_TRY(ensure_cg_workspace(h, L, nblk, 0, cap, L * L));
+    if (!h->d_bcg)
+        ST_TRY(dev_alloc(&h->d_bcg, (size_t)kBcgSmallDoubles));
+    h->last_cg_kernel = "BlockCG-rQ (1 SpMM + 3 passes)";
+    h->last_solver_product = solver_product_kernel_name(h, *plan, splan, L);
+    const int use_cap = hist ? cap : 0;
+    const int saved_cap = h->hist_cap;
+    h->hist_cap = use_cap;  // kernels record only what the caller asked for
+    int poison = 0;
+    ST_TRY(solve_prologue(h, {plan, splan}, &poison));
+    HIP_TRY(launch_bcg_init(h, d_b, d_x, L, tol, nblk));
+    ST_TRY(solve_poison_fill(h, poison));
+    auto iterate = [&](int) -> hipError_t { return launch_bcg_iteration(h, *plan, splan, d_x, L, nblk, tol); };
+    const int K = cg_batch_iters(h->m, h->nnz, L);
+    mspmv_status st = MSPMV_OK;
+    hipGraphExec_t exec = nullptr;
+    if (max_iters >= K && !(poison & MSPMV_POISON_LATE_ZERO)) {
+        const void *tk = nullptr;
+        std::memcpy(&tk, &tol, sizeof tk);
+        std::vector<const void *> key = {
+            d_x, h->d_r, h->d_p0, h->d_ap, h->d_partials, h->d_gtickets, h->d_bcg, h->d_ctrl, h->d_hist, h->stream,
+            plan, splan, tk, reinterpret_cast<const void *>((intptr_t)L),
+            reinterpret_cast<const void *>((intptr_t)nblk), reinterpret_cast<const void *>((intptr_t)use_cap),
+            reinterpret_cast<const void *>((intptr_t)K)};
+        st = solver_graph(h, h->bcg_graph, key, K, iterate, "block CG");
+        exec = h->bcg_graph.exec;
+    }
+    hipEvent_t evs[2] = {nullptr, nullptr};
+    if (st == MSPMV_OK)
+        st = solve_batches(h, K, max_iters, exec, poison, evs, "block CG", iterate);
+    CgControl fin{};
+    ST_TRY(solve_collect(h, st, evs, saved_cap, use_cap, iters, hist, &fin, "block CG"));
+    if (fin.breakdown) {
+        const bool of_g = (fin.breakdown & kBcgBrokeG) != 0;
+        set_error(std::string("block CG breakdown: pivot ") + std::to_string(fin.breakdown & 0xf) + " of " +
+                  (of_g ? "G = S^T A S" : "H = V^T V") + " is <= 0 or non-finite " +
+                  (fin.iter == 0 && !of_g ? "at the init (a zero or dependent right-hand-side column)"
+                                          : "in iteration " + std::to_string(fin.iter - (of_g ? 0 : 1))) +
+                  "; the block is rank deficient -- solve the columns independently with mspmv_dcg_multi");
+        return MSPMV_ERR_BREAKDOWN;
+    }
+    return MSPMV_OK;
+}
+
 // Host-pointer form of a device solve: B up, solve_dev(dB, dX), X down (also after a breakdown: the other
 // columns were solved).
 static mspmv_status solve_host(mspmv_handle h, const double *B, double *X, int L, int *iters,
@@ -784,6 +860,36 @@ mspmv_status mspmv_dbicgstab_multi(mspmv_handle h, const double *B, double *X, i
 {
     return solve_host(h, B, X, L, iters, [&](const double *dB, double *dX) {
         return bicgstab_solve_dev(h, dB, dX, L, max_iters, tolerance, iters, max_err_hist, hist_cap);
+    });
+}
+
+mspmv_status mspmv_solver_pass_shape(mspmv_handle h, int L, int *pass_blocks, int *batch_iters)
+{
+    ST_TRY(check_handle(h));
+    if (!supported_L(L))
+        return (set_error("L must be one of 1, 2, 4, 8, 16"), MSPMV_ERR_UNSUPPORTED);
+    if (pass_blocks)
+        *pass_blocks = cg_update_blocks((long long)h->m * L, h->num_cus);
+    if (batch_iters)
+        *batch_iters = cg_batch_iters(h->m, h->nnz, L);
+    return MSPMV_OK;
+}
+
+mspmv_status mspmv_dbcg_multi_dev(mspmv_handle h, const double *d_B, double *d_X, int L, int max_iters,
+                                  double tolerance, int *iters, double *max_err_hist, int hist_cap)
+{
+    ST_TRY(check_handle(h));
+    return bcg_solve_native(h, d_B, d_X, L, max_iters, tolerance, iters, max_err_hist, hist_cap);
+}
+
+mspmv_status mspmv_dbcg_multi(mspmv_handle h, const double *B, double *X, int L, int max_iters, double tolerance,
+                              int *iters, double *max_err_hist, int hist_cap)
+{
+    if (h && !supported_L(L))  // before the panels are sized by L
+        return (set_error("block CG: L must be one of 1, 2, 4, 8, 16 (the columns are coupled: no column groups)"),
+                MSPMV_ERR_UNSUPPORTED);
+    return solve_host(h, B, X, L, iters, [&](const double *dB, double *dX) {
+        return bcg_solve_native(h, dB, dX, L, max_iters, tolerance, iters, max_err_hist, hist_cap);
     });
 }
 

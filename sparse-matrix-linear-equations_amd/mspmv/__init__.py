@@ -117,6 +117,9 @@ _SIGS = {
     "mspmv_dcg_multi_dev": (_I, [_P, _P, _P, _I, _I, _D, _I, _PI, _P, _I]),
     "mspmv_dbicgstab_multi": (_I, [_P, _P, _P, _I, _I, _D, _PI, _P, _I]),
     "mspmv_dbicgstab_multi_dev": (_I, [_P, _P, _P, _I, _I, _D, _PI, _P, _I]),
+    "mspmv_solver_pass_shape": (_I, [_P, _I, _PI, _PI]),
+    "mspmv_dbcg_multi": (_I, [_P, _P, _P, _I, _I, _D, _PI, _P, _I]),
+    "mspmv_dbcg_multi_dev": (_I, [_P, _P, _P, _I, _I, _D, _PI, _P, _I]),
     "mspmv_spai_values": (_I, [ctypes.POINTER(_CsrD), _P]),
     "mspmv_ic0_nnz": (_I, [ctypes.POINTER(_CsrD), _PI]),
     "mspmv_ic0_factor": (_I, [ctypes.POINTER(_CsrD), _P, _P, _P, _PD]),
@@ -571,8 +574,8 @@ class GpuCsr:
         return lib.mspmv_cg_kernel_name(self.h).decode()
 
     def solver_product_kernel_name(self) -> str:
-        """The kernel the last BiCGSTAB / ILU(0)-BiCGSTAB solve's two products ran
-        (mspmv_solver_product_kernel_name)."""
+        """The kernel the last BiCGSTAB / ILU(0)-BiCGSTAB solve's two products, or the last block CG solve's
+        product, ran (mspmv_solver_product_kernel_name)."""
         return lib.mspmv_solver_product_kernel_name(self.h).decode()
 
     def cg_resident_stamps(self, db: "DeviceBuffer", dx: "DeviceBuffer", max_iters: int, tolerance: float,
@@ -701,6 +704,39 @@ class GpuCsr:
         st = lib.mspmv_dbicgstab_multi_dev(self.h, dB.ptr, dX.ptr, L, max_iters, tolerance, ctypes.byref(it),
                                            _ptr(hist) if hist_cap else None, hist_cap)
         _check(st, "dbicgstab_multi_dev", allow=(4,))
+        return it.value, hist[: min(it.value, hist_cap)], st
+
+    def solver_pass_shape(self, L: int):
+        """(workgroups per streaming solver pass, iterations per batch / cached graph) for panels of native width L
+        (mspmv_solver_pass_shape)."""
+        nb, k = ctypes.c_int(), ctypes.c_int()
+        _check(lib.mspmv_solver_pass_shape(self.h, L, ctypes.byref(nb), ctypes.byref(k)), "solver_pass_shape")
+        return nb.value, k.value
+
+    def block_cg(self, B: np.ndarray, max_iters: int, tolerance: float, hist_cap: int = 0,
+                 allow_fault: bool = False):
+        """Block CG (BCGrQ) for a symmetric positive definite matrix (mspmv_dbcg_multi): the columns share one
+        Krylov space, so iterations fall as L grows.  (X, iterations, history, status); a breakdown (a rank-deficient
+        block: MSPMV_ERR_BREAKDOWN, X the last completed iterate) is returned, not raised.  L in 1, 2, 4, 8, 16."""
+        B = np.ascontiguousarray(B, np.float64)
+        if B.ndim == 1:
+            B = B.reshape(-1, 1)
+        L = B.shape[1]
+        X = np.empty_like(B)
+        it = ctypes.c_int()
+        hist = np.zeros(max(hist_cap, 1), np.float64)
+        st = lib.mspmv_dbcg_multi(self.h, _ptr(B), _ptr(X), L, max_iters, tolerance, ctypes.byref(it),
+                                  _ptr(hist) if hist_cap else None, hist_cap)
+        _check(st, "dbcg_multi", allow=(4, FAULT) if allow_fault else (4,))
+        return X, it.value, hist[: min(it.value, hist_cap)], st
+
+    def block_cg_dev(self, dB: DeviceBuffer, dX: DeviceBuffer, L: int, max_iters: int, tolerance: float,
+                     hist_cap: int = 0):
+        it = ctypes.c_int()
+        hist = np.zeros(max(hist_cap, 1), np.float64)
+        st = lib.mspmv_dbcg_multi_dev(self.h, dB.ptr, dX.ptr, L, max_iters, tolerance, ctypes.byref(it),
+                                      _ptr(hist) if hist_cap else None, hist_cap)
+        _check(st, "dbcg_multi_dev", allow=(4,))
         return it.value, hist[: min(it.value, hist_cap)], st
 
     def pcg_spai(self, m: "GpuCsr", B: np.ndarray, max_iters: int, tolerance: float, hist_cap: int = 0):
