@@ -88,8 +88,9 @@ MSPMV_API int mspmv_device_count(void);
 /* ---- matrix handle ------------------------------------------------------------------ */
 /* Upload the CSR once to HBM on `device` and build its merge-path tile plans.  Replaces
  * the per-call partitioning of OmpMergeCsrmv (cpu_spmv.cpp:379-389) and CUB's
- * DeviceSpmvSearchKernel (dispatch_spmv_orig.cuh:99-143): the matrix is immutable, so the
- * partition is computed once.  `host` arrays are only read during the call. */
+ * DeviceSpmvSearchKernel (dispatch_spmv_orig.cuh:99-143): the matrix's pattern is fixed for the
+ * handle's life, so the partition is computed once (its values can be replaced:
+ * mspmv_csr_update_values).  `host` arrays are only read during the call. */
 MSPMV_API mspmv_status mspmv_csr_create(const mspmv_csr_d *host, int device, mspmv_handle *out);
 /* Same, from arrays already resident in HBM (copied device-to-device). */
 MSPMV_API mspmv_status mspmv_csr_create_dev(const mspmv_csr_d *dev, int device, mspmv_handle *out);
@@ -98,6 +99,36 @@ MSPMV_API mspmv_status mspmv_shape(mspmv_handle h, int *num_rows, int *num_cols,
 /* Milliseconds spent in mspmv_csr_create (upload + partition), the reference's setup_ms
  * (cpu_spmv.cpp:715-742). */
 MSPMV_API double mspmv_setup_ms(mspmv_handle h);
+/* Replace the values of h's matrix; the pattern (row offsets, columns) is unchanged.  values[k] is
+ * entry k of the CSR the handle was created from, same order, num_nonzeros entries.  The loop this
+ * is for: create once, update per time step / Newton iteration / load case, solve.
+ *  - Stream order.  The _dev form is enqueued on the handle's stream and returns without a host
+ *    sync: products and solves enqueued earlier see the old values, everything enqueued later the new
+ *    ones, on every plan.  d_values must stay valid and unchanged until the stream has passed the
+ *    update (mspmv_sync).  The host form copies in, updates, synchronises and records
+ *    mspmv_update_ms.  (A handle's first update uploads the source maps of the reordered plans it
+ *    holds: a blocking copy on the host side, not a wait for the stream.)  A preconditioner handle
+ *    of mspmv_dpcg_spai_multi runs its products on A's stream: synchronise its update before that solve.
+ *  - What is refreshed: the CSR values and every derived copy of every plan built so far, for every
+ *    width (the offset windows' panels and remainder, the column-slab / sliced-ELL / slab-SpMM value
+ *    streams, the register-resident CG's layout).  Plans built later read the new values.
+ *  - What is kept: every plan decision, tile boundary, record, column stream, dictionary, ticket and
+ *    the fault word; the kernel-name and plan queries and mspmv_setup_ms answer as before; cached
+ *    solver graphs stay valid (every buffer they bake in is updated in place).
+ *  - The values are not read on the host and not checked: Inf and NaN are legal, as at create.
+ *    Padding slots of every layout keep their zeros.
+ *  - MSPMV_ERR_INVALID: null handle, or null pointer with num_nonzeros > 0.  num_nonzeros == 0:
+ *    MSPMV_OK, nothing enqueued.  MSPMV_ERR_UNSUPPORTED: a handle whose values belong to another
+ *    handle (a row-range view) or that such views were cut from -- the local matrices inside the
+ *    sharded mspmv_dist_* objects.  A rejected call enqueues nothing.
+ *  - Not refreshed: mspmv_ic0 / mspmv_ilu0 factors (their values come from a host factorisation of
+ *    the caller's matrix: recreate them) and the mspmv_dist_* objects.
+ * A handle that is never updated holds no more device memory and launches nothing else than
+ * before this entry existed. */
+MSPMV_API mspmv_status mspmv_csr_update_values(mspmv_handle h, const double *values);       /* host pointer, synchronous */
+MSPMV_API mspmv_status mspmv_csr_update_values_dev(mspmv_handle h, const double *d_values); /* device pointer, asynchronous */
+/* Wall milliseconds of the last host-pointer update (0 before any), as mspmv_setup_ms. */
+MSPMV_API double mspmv_update_ms(mspmv_handle h);
 /* Block until all work enqueued on the handle's stream has finished. */
 MSPMV_API mspmv_status mspmv_sync(mspmv_handle h);
 /* Confine the handle's work to num_cus compute units (spread evenly over the device's CUs, so

@@ -272,6 +272,30 @@ void release(const Csr &a)
     detail::evict_same_arrays<mspmv_ic0>(detail::factors(), k, [](mspmv_ic0 f) { (void)mspmv_ic0_destroy(f); });
     detail::evict_same_arrays<mspmv_ilu0>(detail::ilu_factors(), k, [](mspmv_ilu0 f) { (void)mspmv_ilu0_destroy(f); });
 }
+// The matrix's values were rewritten in place on the same pattern (a time step, a Newton iteration, a load
+// case): refresh its cached device handle with mspmv_csr_update_values instead of release() + a new upload,
+// so every plan built for it is kept.  The cache owns the handles, so this is the facade's UpdateValues; a
+// matrix not uploaded yet is uploaded.  Factors computed from the old values (IC(0), ILU(0)) are dropped:
+// they are not refreshed (mspmv.h) and are rebuilt on their next use.
+template <typename Csr>
+void UpdateValues(const Csr &a)
+{
+    const detail::Key k = detail::key_of(a);
+    detail::evict_same_arrays<mspmv_ic0>(detail::factors(), k, [](mspmv_ic0 f) { (void)mspmv_ic0_destroy(f); });
+    detail::evict_same_arrays<mspmv_ilu0>(detail::ilu_factors(), k, [](mspmv_ilu0 f) { (void)mspmv_ilu0_destroy(f); });
+    auto &c = detail::handles();
+    for (auto it = c.begin(); it != c.end(); ++it) {
+        const detail::Key &o = it->first;
+        if (o.same_arrays(k) && o.m == k.m && o.n == k.n && o.nnz == k.nnz && o.dev == k.dev) {
+            const mspmv_handle h = it->second;
+            detail::check(mspmv_csr_update_values(h, (const double *)a.values), "mspmv_csr_update_values");
+            c.erase(it);
+            c.emplace(k, h);  // under the new values' fingerprint
+            return;
+        }
+    }
+    (void)detail::handle_for(a);
+}
 inline void release_all()
 {
     for (auto &e : detail::handles())

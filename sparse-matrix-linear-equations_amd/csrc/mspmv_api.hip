@@ -57,7 +57,7 @@ static mspmv_status check_offsets_host(const int *ro, int m, int nnz)
 // are uploaded, the columns and values are the parent's from nonzero view_off on (not copied, not
 // owned; the parent validated them), a->column_indices / values are ignored.
 static mspmv_status create_common(const mspmv_csr_d *a, int device, bool from_device, mspmv_handle *out,
-                                  hipStream_t on_stream = nullptr, const mspmv_handle_s *view_of = nullptr,
+                                  hipStream_t on_stream = nullptr, mspmv_handle_s *view_of = nullptr,
                                   long long view_off = 0)
 {
     if (view_of) {
@@ -191,7 +191,42 @@ static mspmv_status create_common(const mspmv_csr_d *a, int device, bool from_de
         return fail(MSPMV_ERR_HIP);
     }
     h->setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (view_of)
+        ++view_of->num_views;
     *out = h;
+    return MSPMV_OK;
+}
+
+// mspmv_csr_update_values{,_dev}: d_vals again from `values`, then every derived copy of the values the handle
+// holds -- the window panels and remainder (DiaData), the slab value streams (SlabData), the resident CG's ELL.
+// The merge tiles, node blocks (descriptors, records, run-balanced plan), one-wave tiles, 16-bit column streams
+// and dictionaries read d_vals in CSR order and hold no value copy.  All on h's stream, nothing waited for.
+static mspmv_status update_values_common(mspmv_handle_s *h, const double *values, bool from_device)
+{
+    ST_TRY(check_handle(h));
+    if (h->nnz > 0 && !values)
+        return invalid("update_values: null values");
+    if (!h->own_arrays) {
+        set_error("update_values: the handle is a row-range view; its values belong to the handle it was cut from");
+        return MSPMV_ERR_UNSUPPORTED;
+    }
+    if (h->num_views > 0) {
+        set_error("update_values: row-range views were cut from this handle and read its values");
+        return MSPMV_ERR_UNSUPPORTED;
+    }
+    if (h->nnz == 0)
+        return MSPMV_OK;
+    for (auto &kv : h->plans) {  // what can fail for want of memory comes first: a failed update enqueues nothing
+        ST_TRY(prepare_dia_update(kv.second));
+        ST_TRY(prepare_slab_update(kv.second));
+    }
+    HIP_TRY(hipMemcpyAsync(h->d_vals, values, sizeof(double) * (size_t)h->nnz,
+                           from_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    for (auto &kv : h->plans) {
+        ST_TRY(refresh_dia_values(h, kv.second));
+        ST_TRY(refresh_slab_values(h, kv.second));
+    }
+    HIP_TRY(resident_refresh_values(h));
     return MSPMV_OK;
 }
 
@@ -336,6 +371,22 @@ mspmv_status mspmv_shape(mspmv_handle h, int *num_rows, int *num_cols, int *num_
 }
 
 double mspmv_setup_ms(mspmv_handle h) { return h ? h->setup_ms : 0.0; }
+
+mspmv_status mspmv_csr_update_values(mspmv_handle h, const double *values)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    ST_TRY(update_values_common(h, values, false));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->update_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return MSPMV_OK;
+}
+
+mspmv_status mspmv_csr_update_values_dev(mspmv_handle h, const double *d_values)
+{
+    return update_values_common(h, d_values, true);
+}
+
+double mspmv_update_ms(mspmv_handle h) { return h ? h->update_ms : 0.0; }
 
 mspmv_status mspmv_sync(mspmv_handle h)
 {

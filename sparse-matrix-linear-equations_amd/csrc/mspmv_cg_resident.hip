@@ -782,6 +782,16 @@ static bool resident_build(mspmv_handle_s *h, ResidentCg *r)
     return true;
 }
 
+// The fill again: same pattern, so the columns and lengths it rewrites are the ones already there.
+hipError_t resident_refresh_values(mspmv_handle_s *h)
+{
+    ResidentCg *r = h->rcg;
+    if (!r || !r->ok)
+        return hipSuccess;
+    return res_fill(r->rpt, r->nzr, h->d_row_offsets, h->d_cols, h->d_vals, r->d_rb, r->G, r->d_cols, r->d_vals,
+                    r->d_len, h->stream);
+}
+
 mspmv_status resident_prepare(mspmv_handle_s *h, ResidentCg **out)
 {
     *out = h->rcg;

@@ -659,6 +659,7 @@ void free_dia(DiaData *d)
     dia_free(d->d_rem_ptr);
     dia_free(d->d_rem_col);
     dia_free(d->d_rem_val);
+    dia_free(d->d_rem_src);
     delete d;
 }
 
@@ -1006,6 +1007,7 @@ mspmv_status build_dia_plan(mspmv_handle_s *h, TilePlan &p, double min_fill, dou
             set_error(std::string("offset-window plan: remainder fill: ") + hipGetErrorString(e));
             return MSPMV_ERR_HIP;
         }
+        dd->h_rem_src.swap(hp.rem_src);  // kept on the host for a value update (refresh_dia_values)
     }
     if (hipMalloc((void **)&dd->d_vt, sizeof(double) * 128 * (size_t)sump) != hipSuccess) {
         dd->d_vt = nullptr;
@@ -1101,6 +1103,45 @@ hipError_t launch_dia(mspmv_handle_s *h, const TilePlan &plan, const double *d_X
         dia_launch_L<decltype(Lc)::value>(a, s, nt);
         return hipGetLastError();
     });
+}
+
+// The build's two fills again, in the build's order of writes per slot: the panels zeroed, then k_dia_fill
+// (the slots it does not write are the padding and stay zero), and the remainder through its source list.
+mspmv_status prepare_dia_update(TilePlan &plan)
+{
+    DiaData *dd = plan.dia;
+    if (!dd || dd->rem <= 0 || dd->d_rem_src)
+        return MSPMV_OK;
+    const mspmv_status st = dia_upload(&dd->d_rem_src, dd->h_rem_src);
+    if (st != MSPMV_OK) {
+        dia_free(dd->d_rem_src);
+        return st;
+    }
+    std::vector<int>().swap(dd->h_rem_src);
+    return MSPMV_OK;
+}
+
+mspmv_status refresh_dia_values(mspmv_handle_s *h, TilePlan &plan)
+{
+    DiaData *dd = plan.dia;
+    if (!dd)
+        return MSPMV_OK;
+    hipError_t e = hipMemsetAsync(dd->d_vt, 0, sizeof(double) * 128 * (size_t)dd->sum_pairs, h->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_dia_fill, dim3((unsigned)dd->windows), dim3(kDiaThreads), 0, h->stream, h->d_row_offsets,
+                           h->d_cols, h->d_vals, dd->d_hdr, dd->d_off, dd->windows, h->m, dd->d_vt);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && dd->rem > 0) {
+        hipLaunchKernelGGL(k_dia_rem_fill, dim3(1024), dim3(256), 0, h->stream, h->d_vals, dd->d_rem_src, dd->rem,
+                           dd->d_rem_val);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) {
+        set_error(std::string("offset-window value update: ") + hipGetErrorString(e));
+        return MSPMV_ERR_HIP;
+    }
+    return MSPMV_OK;
 }
 
 std::string dia_kernel_name(const mspmv_handle_s *h, int L)

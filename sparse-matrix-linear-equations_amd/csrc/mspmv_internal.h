@@ -120,6 +120,11 @@ struct SlabData {
     uint2 *d_ent = nullptr;             // [entries] {offset in chunk | length << 16, row in block}
     double *d_val = nullptr;            // [nnz + pad] values, slab-major within each block
     unsigned short *d_col = nullptr;    // [nnz + pad] column - slab * kSlabCols (SpMM: - segment's first column)
+    // mspmv_csr_update_values: slot s of d_val holds CSR value src[s], or a padding zero (src[s] < 0).  On the
+    // host from the build (4 B per slot), moved to the device by the first update, where it stays.
+    size_t slots = 0;                   // nnz + pad, without the kNnzPad tail (never rewritten)
+    std::vector<int> h_src;             // [slots] until the first update
+    int *d_src = nullptr;               // [slots rounded up to 4, the tail -1] from the first update on
     double x_bytes_per_nnz = 0.0;       // x (SpMM: panel rows, all L columns) staged per nonzero (plan statistic)
 };
 
@@ -157,6 +162,10 @@ struct DiaData {
     int *d_rem_ptr = nullptr;                // [m + 1] (null when rem == 0)
     int *d_rem_col = nullptr;                // [rem]
     double *d_rem_val = nullptr;             // [rem]
+    // mspmv_csr_update_values: d_rem_val[i] = CSR value rem_src[i].  On the host from the build (the
+    // build's device copy is freed after its fill), uploaded by the first update, where it stays.
+    std::vector<int> h_rem_src;              // [rem] until the first update
+    int *d_rem_src = nullptr;                // [rem] from the first update on
 };
 
 // A merge-path tile plan for one nominal tile size (merge items per tile).
@@ -303,6 +312,8 @@ struct mspmv_handle_s {
     hipStream_t stream = nullptr;
     bool own_stream = true;  // false: a shared CU-masked stream (mspmv_set_cu_limit)
     bool own_arrays = true;  // false: d_cols / d_vals are a row range of another handle's (csr_create_view)
+    int num_views = 0;       // row-range views cut from this handle (they read its d_vals: no value update)
+    double update_ms = 0.0;  // wall ms of the last host-pointer mspmv_csr_update_values
     int m = 0, n = 0, nnz = 0;
     int *d_row_offsets = nullptr;
     int *d_cols = nullptr;
@@ -473,6 +484,11 @@ constexpr int kRunPlanKey = -2;  // the run-balanced node-block SpMV plan (mspmv
 mspmv_status build_slab_plan(mspmv_handle_s *h, TilePlan &p, double min_nnz_per_block = 0.0, int cfg = 0,
                              bool groups = false, int num_groups = 0);  // num_groups 0: MSPMV_SLAB_GROUPS or kSlabGroups
 void free_slab(SlabData *s);
+// mspmv_csr_update_values, every slab plan (SpMV, sliced-ELL, SpMM).  prepare: the plan's source map to the
+// device on the first update (a blocking copy, no stream sync; may fail, enqueues nothing).  refresh, after it:
+// plan.slab->d_val again from h->d_vals through the map, on h's stream.
+mspmv_status prepare_slab_update(TilePlan &plan);
+mspmv_status refresh_slab_values(mspmv_handle_s *h, TilePlan &plan);
 hipError_t launch_slab(mspmv_handle_s *h, const TilePlan &plan, const double *d_x, double *d_y);
 std::string slab_kernel_name(const mspmv_handle_s *h);  // the handle's plain-SpMV slab plan's kernel
 // Column-slab SpMM plans (L = 8, 16), keyed apart from every tile plan.
@@ -493,6 +509,11 @@ constexpr int kDiaPlanKey = -3;
 // panels; p is freed by the caller on any error.
 mspmv_status build_dia_plan(mspmv_handle_s *h, TilePlan &p, double min_fill, double min_window_fill);
 void free_dia(DiaData *d);
+// mspmv_csr_update_values.  prepare: the remainder's source list to the device on the first update (a blocking
+// copy, no stream sync; may fail, enqueues nothing).  refresh, after it: the windows' value panels and remainder
+// values again from h->d_vals, on h's stream.
+mspmv_status prepare_dia_update(TilePlan &plan);
+mspmv_status refresh_dia_values(mspmv_handle_s *h, TilePlan &plan);
 // Y = A X (L = 1, 2, 4, 8, 16; ld: panel stride, 0 = L); ctrl (CG): return at once when ctrl->done;
 // partials (dot mode): also X.(A X) per column per window into partials[windows][L] (launch_fold_dot),
 // with the matrix's rows at X row row_off (a row-range view); stream: 0 = the handle's
@@ -740,6 +761,9 @@ bool cg_resident_enabled();
 bool cg_resident_pipelined();  // the resident kernel's iteration form (MSPMV_CG_RESIDENT_FORM)
 mspmv_status resident_prepare(mspmv_handle_s *h, ResidentCg **out);
 void resident_free(ResidentCg *r);
+// mspmv_csr_update_values: the resident layout's values again from h->d_vals, on h's stream (a layout that
+// does not exist or did not fit: nothing).  The hand-off slots and the abort word are not touched.
+hipError_t resident_refresh_values(mspmv_handle_s *h);
 // d_stamps (diagnostic solves, mspmv_cg_resident_stamps): [stamp_iters][G][5] wall_clock64() phase
 // stamps of every workgroup; null otherwise.
 hipError_t launch_cg_resident(mspmv_handle_s *h, ResidentCg *r, const double *d_b, double *d_x, int max_iters,

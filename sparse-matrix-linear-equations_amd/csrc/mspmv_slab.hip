@@ -625,6 +625,7 @@ void free_slab(SlabData *s)
     slab_free(s->d_slice);
     slab_free(s->d_sent);
     slab_free(s->d_long);
+    slab_free(s->d_src);
     delete s;
 }
 
@@ -647,6 +648,63 @@ static mspmv_status slab_upload(T **d, const std::vector<T> &hsrc, size_t pad = 
     return MSPMV_OK;
 }
 
+// mspmv_csr_update_values: val[s] = src[s] < 0 ? 0.0 : vals[src[s]] over the n4 groups of four slots (the map
+// is padded to whole groups with -1; val's kNnzPad tail takes the zeros a ragged last group writes).  A pure
+// stream but for the gather: each workgroup takes one contiguous slice, as k_stream_read does, the map read
+// once in nontemporal 16-B loads, the values written in 16-B stores.  Within a block the layouts keep CSR order
+// per slab and run, so the gathered lines are reused by neighbouring lanes.
+typedef int v4i_t __attribute__((ext_vector_type(4)));
+__global__ __launch_bounds__(kBlock) void k_slab_gather(const double *__restrict__ vals, const v4i_t *__restrict__ src,
+                                                        long long n4, v2d_t *__restrict__ val)
+{
+    const long long per = (n4 + gridDim.x - 1) / gridDim.x;
+    const long long b = (long long)blockIdx.x * per;
+    const long long e = b + per < n4 ? b + per : n4;
+    for (long long i = b + threadIdx.x; i < e; i += kBlock) {
+        const v4i_t k = __builtin_nontemporal_load(src + i);
+        v2d_t lo, hi;
+        lo.x = k.x < 0 ? 0.0 : vals[k.x];
+        lo.y = k.y < 0 ? 0.0 : vals[k.y];
+        hi.x = k.z < 0 ? 0.0 : vals[k.z];
+        hi.y = k.w < 0 ? 0.0 : vals[k.w];
+        val[2 * i] = lo;
+        val[2 * i + 1] = hi;
+    }
+}
+
+mspmv_status prepare_slab_update(TilePlan &plan)
+{
+    SlabData *s = plan.slab;
+    if (!s || s->slots == 0 || s->d_src)
+        return MSPMV_OK;
+    s->h_src.resize((s->slots + 3) / 4 * 4, -1);  // whole groups of four
+    const mspmv_status st = slab_upload(&s->d_src, s->h_src);
+    if (st != MSPMV_OK) {
+        slab_free(s->d_src);
+        return st;
+    }
+    std::vector<int>().swap(s->h_src);
+    return MSPMV_OK;
+}
+
+mspmv_status refresh_slab_values(mspmv_handle_s *h, TilePlan &plan)
+{
+    SlabData *s = plan.slab;
+    if (!s || s->slots == 0)
+        return MSPMV_OK;
+    const size_t n4 = (s->slots + 3) / 4;  // the last group ends <= 3 slots into the kNnzPad (16) tail
+    const long long groups = ((long long)n4 + kBlock - 1) / kBlock;
+    const unsigned grid = (unsigned)std::max(1LL, std::min(groups, 4LL * h->num_cus));
+    hipLaunchKernelGGL(k_slab_gather, dim3(grid), dim3(kBlock), 0, h->stream, h->d_vals,
+                       reinterpret_cast<const v4i_t *>(s->d_src), (long long)n4, reinterpret_cast<v2d_t *>(s->d_val));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        set_error(std::string("column-slab value update: ") + hipGetErrorString(e));
+        return MSPMV_ERR_HIP;
+    }
+    return MSPMV_OK;
+}
+
 // Per block: its nonzeros [n0, n1) with columns in [clo, chi) in slab-major order (stable within a
 // slab: CSR order), placed at stream position base, cut into chunks of one slab, <= C.chunk nonzeros
 // and <= C.entries runs of one row.
@@ -659,7 +717,7 @@ struct SlabBlockOut {
 
 static void slab_block(const std::vector<int> &ro, const std::vector<int> &ci, const std::vector<double> &va,
                        int r0, int n0, int r1, int n1, int clo, int chi, int base, const SlabCfg &C, double *oval,
-                       unsigned short *ocol, SlabBlockOut &out)
+                       int *osrc, unsigned short *ocol, SlabBlockOut &out)
 {
     const int W = C.cols;
     const int rlast = n1 > ro[(size_t)r1] ? r1 : r1 - 1;  // the trailing partial row, when there is one
@@ -696,6 +754,7 @@ static void slab_block(const std::vector<int> &ro, const std::vector<int> &ci, c
         const int s = ci[(size_t)k] / W;
         const int q = put[(size_t)(s - smin)]++;
         oval[(size_t)base + q] = va[(size_t)k];
+        osrc[(size_t)base + q] = k;
         ocol[(size_t)base + q] = (unsigned short)(ci[(size_t)k] - s * W);
         row[(size_t)q] = kr[(size_t)i];
     }
@@ -836,8 +895,9 @@ static mspmv_status slab_host_matrix(mspmv_handle_s *h, std::vector<int> &ro, st
 // carries and heads: three [T][16] slots, as the tile plans) and tile modes 255.
 static mspmv_status slab_finish(mspmv_handle_s *h, TilePlan &p, int cfg, int groups,
                                 const std::vector<int4> &blk, const std::vector<SlabBlockOut> &outs,
-                                const std::vector<double> &oval, const std::vector<unsigned short> &ocol,
-                                const std::vector<int2> &hb, const std::vector<unsigned char> &hs)
+                                const std::vector<double> &oval, std::vector<int> &osrc,
+                                const std::vector<unsigned short> &ocol, const std::vector<int2> &hb,
+                                const std::vector<unsigned char> &hs)
 {
     const int T = p.num_tiles;
     std::vector<int4> dblk(blk), chunks;
@@ -872,6 +932,8 @@ static mspmv_status slab_finish(mspmv_handle_s *h, TilePlan &p, int cfg, int gro
     s->num_chunks = (int)chunks.size() - 1;
     s->num_entries = (int)ents.size();
     s->x_bytes_per_nnz = (double)staged / (double)h->nnz;
+    s->slots = oval.size();
+    s->h_src.swap(osrc);
     p.slab = s;
     mspmv_status st;
     if ((st = slab_upload(&s->d_blk, dblk)) != MSPMV_OK || (st = slab_upload(&s->d_chunk, chunks)) != MSPMV_OK ||
@@ -921,6 +983,7 @@ struct SellBlockOut {
     std::vector<unsigned short> sents;
     std::vector<int4> longs;
     std::vector<double> val;
+    std::vector<int> src;  // the CSR position of each value, -1 for a padding zero (SlabData::h_src)
     std::vector<unsigned short> col;
     long long staged = 0;
     bool too_many = false;  // a segment with more long-run pieces than the kernel's LDS table holds
@@ -975,6 +1038,7 @@ static void sell_block(const std::vector<int> &ro, const std::vector<int> &ci, c
         auto put_val = [&](size_t at, int q) {
             const int k = ks[(size_t)ord[(size_t)q]];
             o.val[at] = va[(size_t)k];
+            o.src[at] = k;
             o.col[at] = (unsigned short)(ci[(size_t)k] - base);
         };
         // slot s of lane i in a slice of Lm slots per lane: pairs, then an odd last slot alone
@@ -990,6 +1054,7 @@ static void sell_block(const std::vector<int> &ro, const std::vector<int> &ci, c
             } else if (r.len > kSellLongRun) {  // pieces of <= 512 values: {base, length, row, first | count << 16}
                 const size_t base = o.val.size();
                 o.val.resize(base + r.len + (r.len & 1), 0.0);  // even bases: the slices' pair loads
+                o.src.resize(base + r.len + (r.len & 1), -1);
                 o.col.resize(base + r.len + (r.len & 1), 0);
                 for (int j = 0; j < r.len; ++j)
                     put_val(base + j, r.first + j);
@@ -1017,6 +1082,7 @@ static void sell_block(const std::vector<int> &ro, const std::vector<int> &ci, c
             o.sents.resize(o.sents.size() + (size_t)64 * (pack ? K : 2), 0);
             const size_t base = o.val.size();
             o.val.resize(base + (size_t)S * 64, 0.0);
+            o.src.resize(base + (size_t)S * 64, -1);
             o.col.resize(base + (size_t)S * 64, 0);
             for (int t = 0; t < n; ++t) {  // run t: lane t % 64, its k = t / 64
                 const Run &r = shorts[i0 + (size_t)t];
@@ -1051,6 +1117,7 @@ static void sell_block(const std::vector<int> &ro, const std::vector<int> &ci, c
             const int e0 = (int)o.sents.size();
             const size_t base = o.val.size();
             o.val.resize(base + (size_t)Lm * 64, 0.0);
+            o.src.resize(base + (size_t)Lm * 64, -1);
             o.col.resize(base + (size_t)Lm * 64, 0);
             for (int i = 0; i < 8; ++i) {
                 const Run *r = i < n ? &mediums[i0 + (size_t)i] : nullptr;
@@ -1096,6 +1163,7 @@ static mspmv_status sell_finish(mspmv_handle_s *h, TilePlan &p, const std::vecto
     std::vector<int4> blk((size_t)T), segs, longs, slices;
     std::vector<unsigned short> sents;
     std::vector<double> val;
+    std::vector<int> src;
     std::vector<unsigned short> col;
     long long staged = 0;
     for (int t = 0; t < T; ++t) {
@@ -1114,6 +1182,7 @@ static mspmv_status sell_finish(mspmv_handle_s *h, TilePlan &p, const std::vecto
             longs.push_back(make_int4(l.x + vb, l.y, l.z, l.w));
         sents.insert(sents.end(), o.sents.begin(), o.sents.end());
         val.insert(val.end(), o.val.begin(), o.val.end());
+        src.insert(src.end(), o.src.begin(), o.src.end());
         col.insert(col.end(), o.col.begin(), o.col.end());
         const int rb = t / G;
         blk[(size_t)t] = make_int4(rbs[(size_t)rb], rbs[(size_t)rb + 1] - rbs[(size_t)rb], g0, (int)segs.size());
@@ -1127,6 +1196,8 @@ static mspmv_status sell_finish(mspmv_handle_s *h, TilePlan &p, const std::vecto
     s->num_chunks = (int)segs.size() - 1;
     s->num_entries = (int)longs.size();
     s->x_bytes_per_nnz = (double)staged / (double)h->nnz;
+    s->slots = val.size();
+    s->h_src.swap(src);
     for (int t = 0; t < T; ++t) {
         const SellBlockOut &o = outs[(size_t)t];
         s->stats.merge(o.st);
@@ -1267,6 +1338,7 @@ static mspmv_status build_slab_group_plan(mspmv_handle_s *h, TilePlan &p, double
     for (int t = 0; t < T; ++t)
         cnt[(size_t)t + 1] += cnt[(size_t)t];
     std::vector<double> oval((size_t)h->nnz);
+    std::vector<int> osrc((size_t)h->nnz, -1);
     std::vector<unsigned short> ocol((size_t)h->nnz);
     std::vector<SlabBlockOut> outs((size_t)T);
     std::vector<int4> blk((size_t)T);
@@ -1276,10 +1348,10 @@ static mspmv_status build_slab_group_plan(mspmv_handle_s *h, TilePlan &p, double
         int lo, hi;
         crange(g, lo, hi);
         slab_block(ro, ci, va, r0, ro[(size_t)r0], r1, ro[(size_t)r1], lo, hi, (int)cnt[(size_t)t], C, oval.data(),
-                   ocol.data(), outs[(size_t)t]);
+                   osrc.data(), ocol.data(), outs[(size_t)t]);
         blk[(size_t)t] = make_int4(r0, r1 - r0, 0, 0);
     }
-    return slab_finish(h, p, cfg, G, blk, outs, oval, ocol, hb, hs);
+    return slab_finish(h, p, cfg, G, blk, outs, oval, osrc, ocol, hb, hs);
 }
 
 mspmv_status build_slab_plan(mspmv_handle_s *h, TilePlan &p, double min_nnz_per_block, int cfg, bool groups,
@@ -1310,17 +1382,18 @@ mspmv_status build_slab_plan(mspmv_handle_s *h, TilePlan &p, double min_nnz_per_
     if ((st0 = slab_host_matrix(h, ro, ci, va)) != MSPMV_OK)
         return st0;
     std::vector<double> oval((size_t)h->nnz);
+    std::vector<int> osrc((size_t)h->nnz, -1);
     std::vector<unsigned short> ocol((size_t)h->nnz);
     std::vector<SlabBlockOut> outs((size_t)T);
     std::vector<int4> blk((size_t)T);
 #pragma omp parallel for schedule(dynamic, 4)
     for (int t = 0; t < T; ++t) {
         const int2 b0 = hb[(size_t)t], b1 = hb[(size_t)t + 1];
-        slab_block(ro, ci, va, b0.x, b0.y, b1.x, b1.y, 0, 0x7fffffff, b0.y, kSlabCfgs[0], oval.data(), ocol.data(),
-                   outs[(size_t)t]);
+        slab_block(ro, ci, va, b0.x, b0.y, b1.x, b1.y, 0, 0x7fffffff, b0.y, kSlabCfgs[0], oval.data(), osrc.data(),
+                   ocol.data(), outs[(size_t)t]);
         blk[(size_t)t] = make_int4(b0.x, b1.x - b0.x, 0, 0);
     }
-    return slab_finish(h, p, 0, 1, blk, outs, oval, ocol, hb, hs);
+    return slab_finish(h, p, 0, 1, blk, outs, oval, osrc, ocol, hb, hs);
 }
 
 
@@ -1696,7 +1769,7 @@ struct SlabMmBlockOut {
 };
 
 static void slab_mm_block(const SlabMmCfg &cfg, const std::vector<int> &ro, const std::vector<int> &ci,
-                          const std::vector<double> &va, int r0, int n0, int r1, int n1, double *oval,
+                          const std::vector<double> &va, int r0, int n0, int r1, int n1, double *oval, int *osrc,
                           unsigned short *ocol, SlabMmBlockOut &out)
 {
     const int cnt = n1 - n0;
@@ -1736,6 +1809,7 @@ static void slab_mm_block(const SlabMmCfg &cfg, const std::vector<int> &ro, cons
             const int s = seg_of(ci[(size_t)k]);
             const int q = put[(size_t)s]++;
             oval[(size_t)n0 + q] = va[(size_t)k];
+            osrc[(size_t)n0 + q] = k;
             ocol[(size_t)n0 + q] = (unsigned short)(ci[(size_t)k] - seg_lo[(size_t)s]);
             row[(size_t)q] = r - r0;
         }
@@ -1805,12 +1879,14 @@ mspmv_status build_slab_mm_plan(mspmv_handle_s *h, int L, TilePlan &p)
     if ((st = slab_host_matrix(h, ro, ci, va)) != MSPMV_OK)
         return st;
     std::vector<double> oval((size_t)h->nnz);
+    std::vector<int> osrc((size_t)h->nnz, -1);
     std::vector<unsigned short> ocol((size_t)h->nnz);
     std::vector<SlabMmBlockOut> outs((size_t)T);
 #pragma omp parallel for schedule(dynamic, 4)
     for (int t = 0; t < T; ++t) {
         const int2 b0 = hb[(size_t)t], b1 = hb[(size_t)t + 1];
-        slab_mm_block(cfg, ro, ci, va, b0.x, b0.y, b1.x, b1.y, oval.data(), ocol.data(), outs[(size_t)t]);
+        slab_mm_block(cfg, ro, ci, va, b0.x, b0.y, b1.x, b1.y, oval.data(), osrc.data(), ocol.data(),
+                      outs[(size_t)t]);
     }
     std::vector<int4> blk((size_t)T), chunks;
     std::vector<uint2> ents;
@@ -1836,6 +1912,8 @@ mspmv_status build_slab_mm_plan(mspmv_handle_s *h, int L, TilePlan &p)
     s->num_chunks = (int)chunks.size() - 1;
     s->num_entries = (int)ents.size();
     s->x_bytes_per_nnz = (double)staged * 8.0 * L / (double)h->nnz;
+    s->slots = oval.size();
+    s->h_src.swap(osrc);
     for (int t = 0; t < T; ++t) {
         const SlabMmBlockOut &o = outs[(size_t)t];
         s->stats.merge(o.st);

@@ -97,6 +97,9 @@ _SIGS = {
     "mspmv_destroy": (_I, [_P]),
     "mspmv_shape": (_I, [_P, _PI, _PI, _PI]),
     "mspmv_setup_ms": (_D, [_P]),
+    "mspmv_csr_update_values": (_I, [_P, _P]),
+    "mspmv_csr_update_values_dev": (_I, [_P, _P]),
+    "mspmv_update_ms": (_D, [_P]),
     "mspmv_sync": (_I, [_P]),
     "mspmv_check_faults": (_I, [_P]),
     "mspmv_spmv_tile_stamps": (_I, [_P, _P, _P, ctypes.c_size_t, _P, _PI]),
@@ -511,6 +514,31 @@ class GpuCsr:
 
     def sync(self):
         _check(lib.mspmv_sync(self.h), "sync")
+
+    def update_values(self, values: np.ndarray):
+        """Replace the matrix's values on the same pattern (mspmv_csr_update_values): values[k] is entry k of
+        the CSR the handle was created from.  Every plan built so far is refreshed in place and kept;
+        synchronous.  values: num_nonzeros float64 (anything else is a ValueError; nothing is converted)."""
+        if not isinstance(values, np.ndarray) or values.dtype != np.float64:
+            raise ValueError("update_values: values must be a numpy float64 array")
+        if values.shape != (self.num_nonzeros,):
+            raise ValueError(f"update_values: values has shape {values.shape}, expected ({self.num_nonzeros},)")
+        values = np.ascontiguousarray(values)
+        _check(lib.mspmv_csr_update_values(self.h, _ptr(values)), "csr_update_values")
+
+    def update_values_dev(self, dV: "DeviceBuffer", sync: bool = True):
+        """The same from a device buffer of num_nonzeros doubles (mspmv_csr_update_values_dev), enqueued on the
+        handle's stream: work enqueued before it sees the old values, work after it the new ones.  dV must stay
+        unchanged until the stream has passed the update -- synchronised here unless sync=False."""
+        if dV.nbytes < 8 * self.num_nonzeros:
+            raise ValueError(f"update_values_dev: buffer of {dV.nbytes} B, expected {8 * self.num_nonzeros}")
+        _check(lib.mspmv_csr_update_values_dev(self.h, dV.ptr), "csr_update_values_dev")
+        if sync:
+            self.sync()
+
+    def update_ms(self) -> float:
+        """Wall ms of the last update_values (0.0 before any) -- mspmv_update_ms."""
+        return float(lib.mspmv_update_ms(self.h))
 
     def spmv_tile_stamps(self, dX: "DeviceBuffer", dY: "DeviceBuffer", flush_bytes: int = 0) -> np.ndarray:
         """mspmv_spmv_tile_stamps: per-tile wall_clock64() phase stamps of one plain SpMV, [tiles][6]

@@ -4,7 +4,8 @@
 // the CsrMatrix<double,int> field layout (sparse_matrix.h:648-653), OmpMergeCsrmv /
 // OmpMergeCsrmm / CGSolveSingle / CGSolveMultiple (and, at num_vectors = 32 as cpu_spmm_v2 and
 // preconditioner_benchmark default, OmpMergeCsrmm, IncompleteCholesky + PCGSolveMultiple,
-// SparseApproximateInversion + SPAISolveMultiple) with the reference's argument lists.
+// SparseApproximateInversion + SPAISolveMultiple) with the reference's argument lists, and the facade's own
+// UpdateValues after the values were rewritten in place.
 // Prints one line per call; exit code 0 when every result checks out against a host loop.
 #include <cmath>
 #include <cstdio>
@@ -90,8 +91,20 @@ int main()
             delete[] c->values;
         }
         release(mi);
+        // the values rewritten in place on the same pattern: the cached handle is refreshed (UpdateValues), not
+        // replaced; doubling is exact in every product and partial sum, so the product doubles bit for bit
+        for (double &v : va)
+            v *= 2.0;
+        UpdateValues(a);
+        std::vector<double> y2(m);
+        OmpMergeCsrmv(8, a, a.row_offsets + 1, a.column_indices, a.values, x.data(), y2.data());
+        bool upd_ok = true;
+        for (int r = 0; r < m; ++r)
+            upd_ok = upd_ok && y2[r] == 2.0 * y[r];
+        printf("UpdateValues: OmpMergeCsrmv on the doubled values %s twice the first product\n",
+               upd_ok ? "is exactly" : "IS NOT");
         release(a);
-        const bool ok32 = err32 < 1e-12 && itic > 0 && itsp > 0 && !e_ic.empty() && e_ic.back() < 1e-10 &&
+        const bool ok32 = upd_ok && err32 < 1e-12 && itic > 0 && itsp > 0 && !e_ic.empty() && e_ic.back() < 1e-10 &&
                           !e_spai.empty() && e_spai.back() < 1e-10;
         return (err < 1e-12 && it1 > 0 && itm > 0 && !errs.empty() && errs.back() < 1e-10 && ok32) ? 0 : 2;
     } catch (const std::exception &e) {
