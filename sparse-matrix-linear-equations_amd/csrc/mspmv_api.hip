@@ -243,10 +243,11 @@ const char *mspmv_spmv_kernel_name(mspmv_handle h)
     thread_local std::string name;
     if (!h)
         return "";
-    const TilePlan *plan = nullptr;  // settles the handle's plain-SpMV plan (one-wave or not)
+    const TilePlan no_tiles;  // a handle without rows builds no plan: it reports what an empty one would run
+    const TilePlan *plan = nullptr;
     if (h->m > 0 && product_plan(h, 1, &plan) != MSPMV_OK)
         return "";
-    name = spmv_kernel_name(h);
+    name = product_kernel_name(h, plan ? *plan : no_tiles, 1);
     return name.c_str();
 }
 
@@ -264,7 +265,7 @@ const char *mspmv_spmm_kernel_name(mspmv_handle h, int L)
     const TilePlan *plan = nullptr;
     if (product_plan(h, w, &plan) != MSPMV_OK)
         return "";
-    name = spmm_kernel_name(h, *plan, w);
+    name = product_kernel_name(h, *plan, w);
     return name.c_str();
 }
 

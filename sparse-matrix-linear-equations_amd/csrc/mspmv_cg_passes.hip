@@ -781,14 +781,17 @@ bool dia_dot_fused()
 // Y = A X inside a solver's iteration: the plain L-wide product on the plan the solve chose for it (splan: the
 // handle's offset-window or column-slab plan, else null -> the merge tiles of `plan`), with the control word,
 // so the launch returns at once when the solve has stopped.  The split CG and BiCGSTAB launch it.
+static const TilePlan &solver_product_plan(const TilePlan &p, const TilePlan *sp) { return sp ? *sp : p; }
+
 hipError_t launch_solver_product(mspmv_handle_s *h, const TilePlan &plan, const TilePlan *splan, const double *d_X,
                                  double *d_Y, int L)
 {
-    if (splan && splan->dia)
-        return launch_dia(h, *splan, d_X, d_Y, L, L, h->d_ctrl);
-    if (splan && splan->slab)
-        return launch_slab_mm(h, *splan, d_X, d_Y, L, L, h->d_ctrl);
-    return launch_spmm_tile_only(h, plan, d_X, d_Y, L, 0, h->d_ctrl);
+    return launch_spmm_tile_only(h, solver_product_plan(plan, splan), d_X, d_Y, L, L, h->d_ctrl);
+}
+
+std::string solver_product_name(const mspmv_handle_s *h, const TilePlan &plan, const TilePlan *splan, int L)
+{
+    return product_kernel_name(h, solver_product_plan(plan, splan), L);
 }
 
 // splan: the plan the solve chose for the plain L-wide product (cg_solve_native: the offset-window or

@@ -1058,17 +1058,11 @@ mspmv_status build_dia_plan(mspmv_handle_s *h, TilePlan &p, double min_fill, dou
     return MSPMV_OK;
 }
 
-template <int L>
-static void dia_launch_L(const DiaArgs &a, hipStream_t s, bool nt)
+DiaKernel pick_dia(const mspmv_handle_s *h, int L, bool dot) { return {L, stream_nt(h), dot}; }
+
+std::string dia_kernel_name(const DiaKernel &k)
 {
-    const dim3 grid((unsigned)a.groups), block(kDiaThreads);
-    dispatch_bool(nt, [&](auto ntc) {
-        constexpr bool NT = decltype(ntc)::value;
-        if (a.partials)
-            hipLaunchKernelGGL((k_spmm_dia<L, NT, true>), grid, block, 0, s, a);
-        else
-            hipLaunchKernelGGL((k_spmm_dia<L, NT>), grid, block, 0, s, a);
-    });
+    return "k_spmm_dia<" + std::to_string(k.L) + "," + (k.nt ? "true" : "false") + (k.dot ? ",true>" : ">");
 }
 
 hipError_t launch_dia(mspmv_handle_s *h, const TilePlan &plan, const double *d_X, double *d_Y, int L, int ld,
@@ -1097,10 +1091,16 @@ hipError_t launch_dia(mspmv_handle_s *h, const TilePlan &plan, const double *d_X
     a.m = h->m;
     a.n = h->n;
     a.ld = ld > 0 ? ld : L;
-    const bool nt = stream_nt(h);
+    const DiaKernel k = pick_dia(h, L, partials != nullptr);
+    const dim3 grid((unsigned)a.groups), block(kDiaThreads);
     hipStream_t s = stream ? stream : h->stream;
-    return dispatch_L(L, [&](auto Lc) {
-        dia_launch_L<decltype(Lc)::value>(a, s, nt);
+    return dispatch_L(k.L, [&](auto Lc) {
+        dispatch_bool(k.nt, [&](auto ntc) {
+            dispatch_bool(k.dot, [&](auto dot) {
+                hipLaunchKernelGGL((k_spmm_dia<decltype(Lc)::value, decltype(ntc)::value, decltype(dot)::value>), grid,
+                                   block, 0, s, a);
+            });
+        });
         return hipGetLastError();
     });
 }
@@ -1142,11 +1142,6 @@ mspmv_status refresh_dia_values(mspmv_handle_s *h, TilePlan &plan)
         return MSPMV_ERR_HIP;
     }
     return MSPMV_OK;
-}
-
-std::string dia_kernel_name(const mspmv_handle_s *h, int L)
-{
-    return "k_spmm_dia<" + std::to_string(L) + "," + (stream_nt(h) ? "true" : "false") + ">";
 }
 
 }  // namespace mspmv

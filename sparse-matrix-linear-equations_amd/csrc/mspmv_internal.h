@@ -490,7 +490,9 @@ void free_slab(SlabData *s);
 mspmv_status prepare_slab_update(TilePlan &plan);
 mspmv_status refresh_slab_values(mspmv_handle_s *h, TilePlan &plan);
 hipError_t launch_slab(mspmv_handle_s *h, const TilePlan &plan, const double *d_x, double *d_y);
-std::string slab_kernel_name(const mspmv_handle_s *h);  // the handle's plain-SpMV slab plan's kernel
+struct SlabKernel { int cfg; bool nt, pack; };  // launch_slab's pick: k_spmv_slab<nt, cfg>, cfg 2 k_spmv_sell<nt, pack>
+SlabKernel pick_slab(const mspmv_handle_s *h, const TilePlan &plan);
+std::string slab_kernel_name(const SlabKernel &k);
 // Column-slab SpMM plans (L = 8, 16), keyed apart from every tile plan.
 inline int slab_mm_key(int L) { return -(1 << 20) - L; }
 const SlabMmCfg &slab_mm_cfg(int L, int which = -1);  // which < 0: the shipped configuration for L
@@ -498,7 +500,9 @@ mspmv_status build_slab_mm_plan(mspmv_handle_s *h, int L, TilePlan &p);
 // ctrl (CG): the launch returns at once when ctrl->done is set; ld: panel stride (0: L)
 hipError_t launch_slab_mm(mspmv_handle_s *h, const TilePlan &plan, const double *d_X, double *d_Y, int L, int ld,
                           const CgControl *ctrl);
-std::string slab_mm_kernel_name(const mspmv_handle_s *h, const TilePlan &plan);
+struct SlabMmKernel { int cfg; bool nt; };  // k_spmm_slab<cfg, nt>: launch_slab_mm's pick
+SlabMmKernel pick_slab_mm(const mspmv_handle_s *h, const TilePlan &plan);
+std::string slab_mm_kernel_name(const SlabMmKernel &k);
 mspmv_status plan_split_rows(TilePlan &p, const std::vector<int2> &hb, const std::vector<unsigned char> &hs);
 
 // ---- offset windows (mspmv_dia.hip) -------------------------------------------------
@@ -520,7 +524,9 @@ mspmv_status refresh_dia_values(mspmv_handle_s *h, TilePlan &plan);
 hipError_t launch_dia(mspmv_handle_s *h, const TilePlan &plan, const double *d_X, double *d_Y, int L, int ld,
                       const CgControl *ctrl, double *partials = nullptr, long long row_off = 0,
                       hipStream_t stream = nullptr);
-std::string dia_kernel_name(const mspmv_handle_s *h, int L);
+struct DiaKernel { int L; bool nt, dot; };  // k_spmm_dia<L, nt, dot>: launch_dia's pick (dot: it takes partials)
+DiaKernel pick_dia(const mspmv_handle_s *h, int L, bool dot);
+std::string dia_kernel_name(const DiaKernel &k);  // (the dot flag is spelled only when set: false is its default)
 // The pipelined single-RHS CG's SpMV (iteration `parity`) on the windows of `plan` (k_cg1_dia): reads
 // {r_k, p_{k-1}} from rp_old, writes p_k into rp_new, Ap into h->d_ap, the deferred x term into d_x and one
 // p.Ap partial per workgroup into h->d_partials; *nslots = that count, for k_cg1_update's consumer level.
@@ -674,10 +680,9 @@ inline int plan_key(int L) { return L == 16 ? tile_items_for(16) + 1 : tile_item
 int spmv_tile_blocks_per_cu();
 // STREAM-like nontemporal read of `bytes` (16-B words) on stream s (mspmv_time_stream_read).
 hipError_t launch_stream_read(const double *p, size_t bytes, int num_cus, hipStream_t s);
-std::string spmv_kernel_name(const mspmv_handle_s *h);
-std::string spmm_kernel_name(const mspmv_handle_s *h, const TilePlan &plan, int L);
-// the kernel launch_solver_product launches on (plan, splan) at native width L
-std::string solver_product_kernel_name(const mspmv_handle_s *h, const TilePlan &plan, const TilePlan *splan, int L);
+// The kernel launch_spmm_tile_only launches on `plan` at native width L, as rocprofv3 lists it (each kernel
+// family's name is formatted from the pick its launcher launches from; mspmv_*_kernel_name)
+std::string product_kernel_name(const mspmv_handle_s *h, const TilePlan &plan, int L);
 bool stream_nt(const mspmv_handle_s *h);
 
 // ---- runtime -> template dispatch ---------------------------------------------------
@@ -725,6 +730,8 @@ int cg_update_blocks(long long elems, int num_cus);
 // else null -> the merge tiles of plan), stopped by the handle's control word
 hipError_t launch_solver_product(mspmv_handle_s *h, const TilePlan &plan, const TilePlan *splan, const double *d_X,
                                  double *d_Y, int L);
+// ... and the kernel it launches (mspmv_solver_product_kernel_name)
+std::string solver_product_name(const mspmv_handle_s *h, const TilePlan &plan, const TilePlan *splan, int L);
 // BiCGSTAB (mspmv_bicgstab.hip): init (X = 0, R = Rhat = P = B, rho = B.B) and one iteration -- V = A P, the
 // rhat.v pass, the s pass, T = A s, the t.t / t.s pass, the update pass (stop test, beta), the p pass.  R, P, V,
 // T live in h->d_r, d_p0, d_ap, d_p1; Rhat in h->d_rhat.  Partial rows are 2 L wide.

@@ -2418,25 +2418,6 @@ static const Switches &switches()
 constexpr double kNtBytes = 128.0 * 1024 * 1024;
 bool stream_nt(const mspmv_handle_s *h) { return 12.0 * (double)h->nnz + 4.0 * (double)h->m > kNtBytes; }
 
-// The node-block SpMV kernel's run height: the pair form holds KR = 6 rows of values per lane.
-int blk_kr(const TilePlan &p) { return p.blk_rows_max <= 6 ? 6 : 8; }
-
-std::string spmv_kernel_name(const mspmv_handle_s *h)
-{
-    if (h->dia == 1)
-        return dia_kernel_name(h, 1);
-    if (h->spmv_slab == 1)
-        return slab_kernel_name(h);
-    const std::string nt = stream_nt(h) ? "true" : "false";
-    const auto it = h->plans.find(plan_key(1));
-    if (h->spmv_onewave != 1 && it != h->plans.end() && it->second.blk_spmv)
-        return "k_spmv_blk<0," + nt + (it->second.num_tiles_reg == it->second.num_tiles ? ",6,false>" : ",6,true>");
-    if (h->spmv_onewave == 1)
-        return "k_spmv_tile<" + std::to_string(kSpmvIpt) + ",0," + nt + ",64,true,true>";
-    const bool fix = it != h->plans.end() && it->second.num_carries > 0;
-    return "k_spmv_tile<" + std::to_string(kSpmvIpt) + ",0," + nt + ",256,true," + (fix ? "true>" : "false>");
-}
-
 int spmv_items_per_thread() { return kSpmvIpt; }
 
 // SpMM tile depth: measured best 8 items per lane group for L <= 4 (fem-blocked pwtk shape,
@@ -2444,54 +2425,7 @@ int spmv_items_per_thread() { return kSpmvIpt; }
 // rows -- one round of the 64 row groups -- 439 us vs 467 at 16, 455 at 28, 550 at 32, r04ai; pwtk
 // shape flat) and 32 for L = 16 (cant shape: 39.2 -> 28.0 us -- half the tile start-ups at 6
 // workgroups per CU instead of 7, r04aa).
-int spmm_iptg_for(int L) { return L >= 16 ? 32 : L >= 8 ? 24 : 8; }
-
-// The kernel a plain SpMM of native width L (1, 2, 4, 8, 16) launches on `plan` (product_plan's
-// choice for L), spelled as rocprofv3 lists it: launch_spmm_L's dispatch, restated.
-std::string spmm_kernel_name(const mspmv_handle_s *h, const TilePlan &plan, int L)
-{
-    if (L == 1)
-        return spmv_kernel_name(h);
-    if (plan.dia)
-        return dia_kernel_name(h, L);
-    if (plan.slab)
-        return slab_mm_kernel_name(h, plan);
-    const std::string nt = stream_nt(h) ? "true" : "false";
-    if (plan.d_blk && plan.num_tiles_reg == plan.num_tiles && spmm_blk_enabled())
-        return "k_spmm_blk<" + std::to_string(L) + ",0," + nt + "," + std::to_string(blk_kr(plan)) + ">";
-    const int iptg = spmm_iptg_for(L);
-    const bool dict = spmm_dict_max(L) > 0 && plan.d_dict;
-    return "k_spmm_tile<" + std::to_string(L) + "," + std::to_string(iptg) + ",0," + nt +
-           (dict ? ",true,true>" : plan.num_carries > 0 ? ",false,true>" : ",false,false>");
-}
-
-// The kernel launch_solver_product launches for a solve's two products of native width L on (plan, splan),
-// spelled as rocprofv3 lists it: launch_solver_product -> launch_spmm_tile_only -> launch_tile<kModeSpmv>,
-// restated.  Unlike spmm_kernel_name it never names the plain SpMV's own plans (one-wave tiles, sliced ELL,
-// run-balanced node blocks), which no solver multiplies on.
-std::string solver_product_kernel_name(const mspmv_handle_s *h, const TilePlan &plan, const TilePlan *splan, int L)
-{
-    if (splan && splan->dia)
-        return dia_kernel_name(h, L);
-    if (splan && splan->slab)
-        return slab_mm_kernel_name(h, *splan);
-    const std::string nt = stream_nt(h) ? "true" : "false";
-    const bool fix = plan.num_carries > 0;  // make_args: TileArgs::fix
-    const bool all_reg = plan.d_blk && plan.num_tiles_reg == plan.num_tiles && (L == 1 || spmm_blk_enabled());
-    if (L == 1) {  // launch_spmv_1<kModeSpmv>
-        if (plan.blk_spmv)
-            return "k_spmv_blk<0," + nt + (all_reg ? ",6,false>" : ",6,true>");
-        const std::string head = "k_spmv_tile<" + std::to_string(kSpmvIpt) + ",0," + nt;
-        if (plan.lanes == 64)
-            return head + ",64,true,true>";
-        return head + ",256,true," + (fix ? "true>" : "false>");
-    }
-    if (all_reg)  // launch_spmm_L
-        return "k_spmm_blk<" + std::to_string(L) + ",0," + nt + "," + std::to_string(blk_kr(plan)) + ">";
-    const bool dict = spmm_dict_max(L) > 0 && plan.d_dict;
-    return "k_spmm_tile<" + std::to_string(L) + "," + std::to_string(spmm_iptg_for(L)) + ",0," + nt +
-           (dict ? ",true,true>" : fix ? ",false,true>" : ",false,false>");
-}
+constexpr int spmm_iptg_for(int L) { return L >= 16 ? 32 : L >= 8 ? 24 : 8; }
 
 // Resident workgroups per CU of a kBlock-thread kernel from its own resources on gfx950: 160 KiB
 // of LDS per CU, 512 VGPRs per SIMD lane (granule 8), at most 8 waves per SIMD, 4 SIMDs.
@@ -2632,7 +2566,7 @@ hipError_t launch_tile_modes(const int *d_row_offsets, const int2 *d_bounds, con
     return hipGetLastError();
 }
 
-static TileArgs make_args(mspmv_handle_s *h, const TilePlan &plan, const double *X, double *Y, int L)
+static TileArgs make_args(const mspmv_handle_s *h, const TilePlan &plan, const double *X, double *Y, int L)
 {
     TileArgs a{};
     a.row_offsets = h->d_row_offsets;
@@ -2675,87 +2609,141 @@ static TileArgs make_args(mspmv_handle_s *h, const TilePlan &plan, const double 
     return a;
 }
 
-template <int LL, int I, int MODE>
-static void launch_spmm_nt(const TileArgs &a, hipStream_t s, bool nt)
-{
-    if constexpr (MODE != kModeCg) {
-        const dim3 grid(a.num_tiles), block(kBlock);
-        dispatch_bool(nt, [&](auto ntc) {
-            constexpr bool NT = decltype(ntc)::value;
-            if constexpr (spmm_dict_max(LL) > 0) {  // plans with column dictionaries (L = 16; L = 8 when enabled)
-                if (a.dict) {
-                    ggl(k_spmm_tile<LL, I, MODE, NT, true>, grid, block, s, a);
-                    return;
-                }
-            }
-            if (MODE == kModeSpmv && !a.fix)  // no split rows: the form without close_split_rows
-                ggl(k_spmm_tile<LL, I, MODE, NT, false, false>, grid, block, s, a);
-            else
-                ggl(k_spmm_tile<LL, I, MODE, NT>, grid, block, s, a);
-        });
-    }
-}
+// Which tile-kernel instantiation a launch runs: decided once, by pick_tile_kernel; launch_tile launches from it
+// and tile_kernel_name spells it.  Fields a kernel has no argument for keep the values set here.
+enum TileKind : int { kTileNone, kSpmvTile, kSpmvBlk, kSpmmTile, kSpmmBlk };
+struct TileKernel {
+    TileKind kind;       // kTileNone: no kernel (the pipelined CG's mode exists for L == 1 only)
+    int L, mode;
+    bool nt;
+    int tb = kBlock;     // k_spmv_tile TB: threads sharing a tile
+    bool blk = true;     // k_spmv_tile BLK: node-block staging compiled in
+    bool fix = true;     // k_spmv_tile / k_spmm_tile FIX: close_split_rows compiled in
+    bool dict = false;   // k_spmm_tile DICT
+    bool fb = false;     // k_spmv_blk FB: the register fallback for tiles that are no register run tiles
+    int kr = kBlkRows;   // k_spmv_blk / k_spmm_blk KR: rows of values a lane holds per run
+};
 
-template <int LL, int MODE>
-static void launch_spmm_L(const TileArgs &a, hipStream_t s, bool nt)
+static TileKernel pick_tile_kernel(const TileArgs &a, int L, int mode, bool nt)
 {
-    if constexpr (MODE != kModeCg) {
-        if (a.all_reg) {  // a node-block plan (single-RHS tiles): every tile a register run tile
-            const dim3 grid(a.num_tiles), block(kBlock);
-            dispatch_bool(nt, [&](auto ntc) {
-                constexpr bool NT = decltype(ntc)::value;
-                if (a.blk_rows_max <= 6)
-                    ggl(k_spmm_blk<LL, MODE, NT, 6>, grid, block, s, a);
-                else
-                    ggl(k_spmm_blk<LL, MODE, NT>, grid, block, s, a);
-            });
-            return;
-        }
-    }
-    launch_spmm_nt<LL, (LL >= 16 ? 32 : LL >= 8 ? 24 : 8), MODE>(a, s, nt);
-}
-
-template <int MODE>
-static void launch_spmv_1(const TileArgs &a, hipStream_t s, bool nt)
-{
-    const dim3 grid(a.num_tiles), block(kBlock);
-    dispatch_bool(nt, [&](auto ntc) {
-        constexpr bool NT = decltype(ntc)::value;
-        if (MODE == kModeSpmv && a.blk_spmv) {
+    TileKernel k{kTileNone, L, mode, nt};
+    if (mode == kModeCg && L != 1)
+        return k;
+    if (L == 1) {
+        if (mode == kModeSpmv && a.blk_spmv) {
             // a node-block plan (every tile, or most: the rest run the kernel's register fallback):
             // the LDS-free kernel, column pairs, runs of <= 6 rows
-            if (a.all_reg)  // every tile a register run tile: no register fallback compiled in
-                ggl(k_spmv_blk<kModeSpmv, NT, 6>, grid, block, s, a);
-            else
-                ggl(k_spmv_blk<kModeSpmv, NT, 6, true>, grid, block, s, a);
-        } else if (MODE == kModeDot && a.all_reg) {
-            // every tile a register node-block tile, dot mode (the row-sharded CG): column owners
-            ggl(k_spmv_blk<kModeDot, NT>, grid, block, s, a);
-        } else if (MODE == kModeSpmv && a.tb == 64) {  // one-wave tiles (skewed rows, spmv_plan)
-            ggl(k_spmv_tile<kSpmvIpt, kModeSpmv, NT, 64>, grid, dim3(64), s, a);
-        } else if (MODE == kModeCg && !a.blk) {  // the pipelined CG without node blocks: fewer VGPRs
-            ggl(k_spmv_tile<kSpmvIpt, MODE, NT, kBlock, false>, grid, block, s, a);
-        } else if (MODE == kModeSpmv && !a.fix) {  // no split rows: the form without close_split_rows
-            ggl(k_spmv_tile<kSpmvIpt, MODE, NT, kBlock, true, false>, grid, block, s, a);
+            k.kind = kSpmvBlk;
+            k.kr = 6;
+            k.fb = !a.all_reg;  // every tile a register run tile: no register fallback compiled in
+        } else if (mode == kModeDot && a.all_reg) {
+            k.kind = kSpmvBlk;  // every tile a register node-block tile, dot mode (the row-sharded CG): column owners
         } else {
-            ggl(k_spmv_tile<kSpmvIpt, MODE, NT>, grid, block, s, a);
+            k.kind = kSpmvTile;
+            if (mode == kModeSpmv && a.tb == 64)  // one-wave tiles (skewed rows, spmv_plan)
+                k.tb = 64;
+            else if (mode == kModeCg && !a.blk)  // the pipelined CG without node blocks: fewer VGPRs
+                k.blk = false;
+            else if (mode == kModeSpmv && !a.fix)  // no split rows: the form without close_split_rows
+                k.fix = false;
         }
-    });
+    } else if (a.all_reg) {  // a node-block plan (single-RHS tiles): every tile a register run tile
+        k.kind = kSpmmBlk;
+        k.kr = a.blk_rows_max <= 6 ? 6 : kBlkRows;
+    } else {
+        k.kind = kSpmmTile;
+        k.dict = spmm_dict_max(L) > 0 && a.dict;  // plans with column dictionaries (L = 16; L = 8 when enabled)
+        k.fix = k.dict || mode != kModeSpmv || a.fix;  // no split rows: the form without close_split_rows
+    }
+    return k;
 }
 
-// MODE 1 (pipelined single-RHS CG) exists for L == 1 in the one-tile kernel only.
+// The kernel as rocprofv3 lists it.  (k_spmv_tile's trailing STAMP is left to its default, as the recorded
+// profiles and bench.py's attribution spell it.)
+static std::string tile_kernel_name(const TileKernel &k)
+{
+    auto b = [](bool v) { return v ? ",true" : ",false"; };
+    auto i = [](int v) { return "," + std::to_string(v); };
+    const std::string L = std::to_string(k.L), mode_nt = i(k.mode) + b(k.nt);
+    switch (k.kind) {
+    case kSpmvTile: return "k_spmv_tile<" + std::to_string(kSpmvIpt) + mode_nt + i(k.tb) + b(k.blk) + b(k.fix) + ">";
+    case kSpmvBlk: return "k_spmv_blk<" + std::to_string(k.mode) + b(k.nt) + i(k.kr) + b(k.fb) + ">";
+    case kSpmmTile: return "k_spmm_tile<" + L + i(spmm_iptg_for(k.L)) + mode_nt + b(k.dict) + b(k.fix) + ">";
+    case kSpmmBlk: return "k_spmm_blk<" + L + mode_nt + i(k.kr) + ">";
+    default: return "";
+    }
+}
+
+// One instantiation each: launched when it is the one k names (false: it is not).
+template <int MODE, bool NT, int TB, bool BLK, bool FIX>
+static bool run_spmv_tile(const TileKernel &k, const TileArgs &a, hipStream_t s)
+{
+    if (k.kind != kSpmvTile || k.tb != TB || k.blk != BLK || k.fix != FIX)
+        return false;
+    ggl(k_spmv_tile<kSpmvIpt, MODE, NT, TB, BLK, FIX>, dim3(a.num_tiles), dim3(TB), s, a);
+    return true;
+}
+template <int MODE, bool NT, int KR, bool FB>
+static bool run_spmv_blk(const TileKernel &k, const TileArgs &a, hipStream_t s)
+{
+    if (k.kind != kSpmvBlk || k.kr != KR || k.fb != FB)
+        return false;
+    ggl(k_spmv_blk<MODE, NT, KR, FB>, dim3(a.num_tiles), dim3(kBlock), s, a);
+    return true;
+}
+template <int LL, int MODE, bool NT, bool DICT, bool FIX>
+static bool run_spmm_tile(const TileKernel &k, const TileArgs &a, hipStream_t s)
+{
+    if (k.kind != kSpmmTile || k.dict != DICT || k.fix != FIX)
+        return false;
+    ggl(k_spmm_tile<LL, spmm_iptg_for(LL), MODE, NT, DICT, FIX>, dim3(a.num_tiles), dim3(kBlock), s, a);
+    return true;
+}
+template <int LL, int MODE, bool NT, int KR>
+static bool run_spmm_blk(const TileKernel &k, const TileArgs &a, hipStream_t s)
+{
+    if (k.kind != kSpmmBlk || k.kr != KR)
+        return false;
+    ggl(k_spmm_blk<LL, MODE, NT, KR>, dim3(a.num_tiles), dim3(kBlock), s, a);
+    return true;
+}
+
+// The instantiations that exist for (MODE, LL, NT), each tried against the pick: a pick outside them launches
+// nothing and is an error, never another kernel.
+template <int MODE, int LL, bool NT>
+static bool launch_picked(const TileKernel &k, const TileArgs &a, hipStream_t s)
+{
+    bool ok = false;
+    if constexpr (LL == 1) {  // k_spmv_tile<.., TB, BLK, FIX>, k_spmv_blk<.., KR, FB>
+        ok = run_spmv_tile<MODE, NT, kBlock, true, true>(k, a, s);
+        if constexpr (MODE == kModeSpmv)
+            ok = ok || run_spmv_tile<MODE, NT, kBlock, true, false>(k, a, s) ||
+                 run_spmv_tile<MODE, NT, 64, true, true>(k, a, s) || run_spmv_blk<MODE, NT, 6, false>(k, a, s) ||
+                 run_spmv_blk<MODE, NT, 6, true>(k, a, s);
+        if constexpr (MODE == kModeCg)
+            ok = ok || run_spmv_tile<MODE, NT, kBlock, false, true>(k, a, s);
+        if constexpr (MODE == kModeDot)
+            ok = ok || run_spmv_blk<MODE, NT, kBlkRows, false>(k, a, s);
+    } else if constexpr (MODE != kModeCg) {  // k_spmm_tile<.., DICT, FIX>, k_spmm_blk<.., KR>
+        ok = run_spmm_tile<LL, MODE, NT, false, true>(k, a, s) || run_spmm_blk<LL, MODE, NT, 6>(k, a, s) ||
+             run_spmm_blk<LL, MODE, NT, kBlkRows>(k, a, s);
+        if constexpr (MODE == kModeSpmv)
+            ok = ok || run_spmm_tile<LL, MODE, NT, false, false>(k, a, s);
+        if constexpr (spmm_dict_max(LL) > 0)  // plans with column dictionaries (L = 16; L = 8 when enabled)
+            ok = ok || run_spmm_tile<LL, MODE, NT, true, true>(k, a, s);
+    }
+    return ok;
+}
+
 template <int MODE>
 static hipError_t launch_tile(const TileArgs &a, int L, hipStream_t s, bool nt)
 {
-    if (MODE == kModeCg && L != 1)
-        return hipErrorInvalidValue;
+    const TileKernel k = pick_tile_kernel(a, L, MODE, nt);
     return dispatch_L(L, [&](auto Lc) {
-        constexpr int LL = decltype(Lc)::value;
-        if constexpr (LL == 1)
-            launch_spmv_1<MODE>(a, s, nt);
-        else
-            launch_spmm_L<LL, MODE>(a, s, nt);
-        return hipGetLastError();
+        const bool ok = dispatch_bool(nt, [&](auto ntc) {
+            return launch_picked<MODE, decltype(Lc)::value, decltype(ntc)::value>(k, a, s);
+        });
+        return ok ? hipGetLastError() : hipErrorInvalidValue;
     });
 }
 
@@ -2802,6 +2790,17 @@ hipError_t launch_spmm_tile_only(mspmv_handle_s *h, const TilePlan &plan, const 
         a.fault = &ctrl->fault;
     }
     return launch_tile<kModeSpmv>(a, L, h->stream, stream_nt(h));
+}
+
+// The kernel launch_spmm_tile_only launches for a product of native width L on `plan`, as rocprofv3 lists it:
+// its three steps, each name formatted from the pick its launcher launches from.
+std::string product_kernel_name(const mspmv_handle_s *h, const TilePlan &plan, int L)
+{
+    if (plan.dia)
+        return dia_kernel_name(pick_dia(h, L, false));
+    if (plan.slab)
+        return L == 1 ? slab_kernel_name(pick_slab(h, plan)) : slab_mm_kernel_name(pick_slab_mm(h, plan));
+    return tile_kernel_name(pick_tile_kernel(make_args(h, plan, nullptr, nullptr, L), L, kModeSpmv, stream_nt(h)));
 }
 
 // The pipelined single-RHS CG's SpMV (iteration `parity`) on the tiles of `plan` (k_spmv_tile MODE 1;

@@ -556,26 +556,30 @@ hipError_t launch_slab(mspmv_handle_s *h, const TilePlan &plan, const double *d_
     a.lng = s.d_long;
     if (plan.num_tiles == 0)
         return hipSuccess;
-    const bool nt = stream_nt(h);
-    const dim3 grid(plan.num_tiles);
-    if (s.cfg == 2) {
-        const dim3 tb(kSlabCfgs[2].threads);
-        dispatch_bool(nt, [&](auto ntc) {
-            dispatch_bool(s.pack, [&](auto pack) {
-                hipLaunchKernelGGL((k_spmv_sell<decltype(ntc)::value, decltype(pack)::value>), grid, tb, 0, h->stream, a);
-            });
-        });
-        return hipGetLastError();
-    }
-    const dim3 b1(kSlabCfgs[1].threads), b0(kSlabCfgs[0].threads);
-    dispatch_bool(nt, [&](auto ntc) {
+    const SlabKernel k = pick_slab(h, plan);
+    const dim3 grid(plan.num_tiles), tb(kSlabCfgs[k.cfg].threads);
+    dispatch_bool(k.nt, [&](auto ntc) {
         constexpr bool NT = decltype(ntc)::value;
-        if (s.cfg == 1)
-            hipLaunchKernelGGL((k_spmv_slab<NT, 1>), grid, b1, 0, h->stream, a);
+        if (k.cfg == 2)
+            dispatch_bool(k.pack, [&](auto pack) {
+                hipLaunchKernelGGL((k_spmv_sell<NT, decltype(pack)::value>), grid, tb, 0, h->stream, a);
+            });
+        else if (k.cfg == 1)
+            hipLaunchKernelGGL((k_spmv_slab<NT, 1>), grid, tb, 0, h->stream, a);
         else
-            hipLaunchKernelGGL((k_spmv_slab<NT, 0>), grid, b0, 0, h->stream, a);
+            hipLaunchKernelGGL((k_spmv_slab<NT, 0>), grid, tb, 0, h->stream, a);
     });
     return hipGetLastError();
+}
+
+SlabKernel pick_slab(const mspmv_handle_s *h, const TilePlan &p) { return {p.slab->cfg, stream_nt(h), p.slab->pack}; }
+
+std::string slab_kernel_name(const SlabKernel &k)
+{
+    const std::string nt = k.nt ? "true" : "false";
+    if (k.cfg == 2)
+        return "k_spmv_sell<" + nt + "," + (k.pack ? "true" : "false") + ">";
+    return "k_spmv_slab<" + nt + "," + std::to_string(k.cfg) + ">";
 }
 
 #ifdef MSPMV_SELL_LAB_STAMPS
@@ -592,16 +596,6 @@ extern "C" __attribute__((visibility("default"))) int mspmv_lab_sell_stamps(unsi
                : -1;
 }
 #endif
-
-std::string slab_kernel_name(const mspmv_handle_s *h)
-{
-    const auto it = h->plans.find(kSlabPlanKey);
-    const SlabData *sd = it != h->plans.end() ? it->second.slab : nullptr;
-    const int cfg = sd ? sd->cfg : 0;
-    if (cfg == 2)
-        return std::string("k_spmv_sell<") + (stream_nt(h) ? "true" : "false") + "," + (sd->pack ? "true" : "false") + ">";
-    return std::string("k_spmv_slab<") + (stream_nt(h) ? "true" : "false") + "," + std::to_string(cfg) + ">";
-}
 
 template <typename T>
 static void slab_free(T *&p)
@@ -1741,21 +1735,22 @@ hipError_t launch_slab_mm(mspmv_handle_s *h, const TilePlan &plan, const double 
     a.head_pub = a.head_val + (size_t)std::max(plan.num_tiles, 1) * plan.carry_L;
     if (plan.num_tiles == 0)
         return hipSuccess;
-    const bool nt = stream_nt(h);
-    switch (s.cfg) {
-    case 0: launch_slab_mm_cfg<0>(a, nt, h->stream); break;
-    case 1: launch_slab_mm_cfg<1>(a, nt, h->stream); break;
-    case 2: launch_slab_mm_cfg<2>(a, nt, h->stream); break;
-    case 3: launch_slab_mm_cfg<3>(a, nt, h->stream); break;
+    const SlabMmKernel k = pick_slab_mm(h, plan);
+    switch (k.cfg) {
+    case 0: launch_slab_mm_cfg<0>(a, k.nt, h->stream); break;
+    case 1: launch_slab_mm_cfg<1>(a, k.nt, h->stream); break;
+    case 2: launch_slab_mm_cfg<2>(a, k.nt, h->stream); break;
+    case 3: launch_slab_mm_cfg<3>(a, k.nt, h->stream); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }
 
-std::string slab_mm_kernel_name(const mspmv_handle_s *h, const TilePlan &plan)
+SlabMmKernel pick_slab_mm(const mspmv_handle_s *h, const TilePlan &plan) { return {plan.slab->cfg, stream_nt(h)}; }
+
+std::string slab_mm_kernel_name(const SlabMmKernel &k)
 {
-    return "k_spmm_slab<" + std::to_string(plan.slab ? plan.slab->cfg : 0) + "," + (stream_nt(h) ? "true" : "false") +
-           ">";
+    return "k_spmm_slab<" + std::to_string(k.cfg) + "," + (k.nt ? "true" : "false") + ">";
 }
 
 // Per block: its nonzeros [n0, n1) reordered by column segment (CSR order within it), cut into chunks

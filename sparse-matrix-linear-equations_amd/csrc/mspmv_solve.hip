@@ -598,7 +598,7 @@ static mspmv_status bicgstab_solve_native(mspmv_handle_s *h, const double *d_b, 
     if (ilu && ilu->num_colors > 0)
         h->last_cg_kernel =
             "MC-ILU0-BiCGSTAB (2 SpMM + 4 sweeps of " + std::to_string(ilu->num_colors) + " colours + 5 passes)";
-    h->last_solver_product = solver_product_kernel_name(h, *plan, splan, L);
+    h->last_solver_product = solver_product_name(h, *plan, splan, L);
     const int use_cap = hist ? cap : 0;
     const int saved_cap = h->hist_cap;
     h->hist_cap = use_cap;  // kernels record only what the caller asked for
@@ -697,7 +697,7 @@ static mspmv_status bcg_solve_native(mspmv_handle_s *h, const double *d_b, doubl
     if (!h->d_bcg)
         ST_TRY(dev_alloc(&h->d_bcg, (size_t)kBcgSmallDoubles));
     h->last_cg_kernel = "BlockCG-rQ (1 SpMM + 3 passes)";
-    h->last_solver_product = solver_product_kernel_name(h, *plan, splan, L);
+    h->last_solver_product = solver_product_name(h, *plan, splan, L);
     const int use_cap = hist ? cap : 0;
     const int saved_cap = h->hist_cap;
     h->hist_cap = use_cap;  // kernels record only what the caller asked for
