@@ -141,6 +141,46 @@ MSPMV_API mspmv_status mspmv_sync(mspmv_handle h);
  * queue of its own; a process has few).  Synchronizes the handle first. */
 MSPMV_API mspmv_status mspmv_set_cu_limit(mspmv_handle h, int num_cus);
 
+/* ---- Infinity-Cache leases ------------------------------------------------------------ */
+/* Every product kernel exists in two forms: one reads the matrix's own arrays (values, columns,
+ * records, panels) with default-policy loads, so their lines stay in the 256 MiB Infinity Cache for
+ * the next product on the same matrix; the other reads them nontemporal, so a matrix that cannot stay
+ * anyway does not evict x / X or another matrix's lines.  Which form a handle runs is decided from the
+ * bytes one product on it streams from those arrays (the largest over the plans the handle has built;
+ * x, y and solver vectors are not counted) against a budget the handles alive on one device share:
+ *   - a stream of at most the floor (32 MiB, the eight L2s together) keeps default-policy loads and
+ *     books nothing;
+ *   - otherwise the handle asks the device's ledger for a lease of that size when its plain product's
+ *     plan is decided (at creation) and again when a later plan streams more: granted while the live
+ *     leases plus the request stay within the budget (default loads), refused otherwise (nontemporal
+ *     loads, and the handle holds no lease).  First come, first served; returned at mspmv_destroy.
+ * mspmv_set_cache_policy overrides the decision for one handle: MSPMV_CACHE_RESIDENT books the
+ * stream whatever the budget says (later handles see it), MSPMV_CACHE_STREAM returns the lease,
+ * MSPMV_CACHE_AUTO asks again.  It synchronizes the handle and drops its cached solver graphs (a
+ * captured graph holds one instantiation); mspmv_spmv_kernel_name and mspmv_cg_kernel_name follow.
+ * The handles inside a sharded object (mspmv_dist_create*) take no lease: under MSPMV_CACHE_AUTO they read
+ * nontemporal when 12 nnz + 4 m of the rank's block exceeds 128 MiB, as every handle did before the ledger.
+ * Results do not depend on the policy: both forms compute the same bits. */
+enum { MSPMV_CACHE_AUTO = 0, MSPMV_CACHE_STREAM = 1, MSPMV_CACHE_RESIDENT = 2 };
+MSPMV_API mspmv_status mspmv_set_cache_policy(mspmv_handle h, int policy);
+/* *resident = 1 when h's products read the matrix with default-policy loads; *bytes = what one plain
+ * single-RHS product streams from the matrix's arrays on its plan (the lease covers the largest plan built,
+ * which may be another: a solver's, a wider product's).  Either pointer may be NULL. */
+MSPMV_API mspmv_status mspmv_cache_info(mspmv_handle h, int *resident, long long *bytes);
+/* The budget of `device`'s ledger in bytes (built-in default, or MSPMV_CACHE_MIB read once per
+ * process); bytes < 0 queries only; *old (may be NULL) takes the value before the call.  Decisions
+ * already made stay as they are.  mspmv_cache_floor: the same for the floor below which nothing is
+ * booked.  Neither needs a device. */
+MSPMV_API mspmv_status mspmv_cache_budget(int device, long long bytes, long long *old);
+MSPMV_API mspmv_status mspmv_cache_floor(int device, long long bytes, long long *old);
+/* The ledger itself, host only (the handles' calls; exposed for tests): exchanges a lease of `held`
+ * bytes (0: none) on `device` for one of `want` bytes under `policy`.  *granted = the bytes booked
+ * after the call (0: no lease), *resident = the load policy that follows.  mspmv_cache_leased: the sum
+ * of the live leases. */
+MSPMV_API mspmv_status mspmv_cache_lease(int device, long long held, long long want, int policy,
+                                         long long *granted, int *resident);
+MSPMV_API mspmv_status mspmv_cache_leased(int device, long long *bytes);
+
 /* ---- merge-path partition ----------------------------------------------------------- */
 /* Coordinates of the num_parts+1 partition boundaries exactly as OmpMergeCsrmv computes
  * them: diagonal_t = min(ceil((m+nnz)/P) * t, m+nnz), MergePathSearch over
@@ -619,7 +659,7 @@ MSPMV_API mspmv_status mspmv_offset_windows(const mspmv_csr_d *a, double min_fil
 MSPMV_API mspmv_status mspmv_spmv_tile_stamps(mspmv_handle h, const double *d_x, double *d_y, size_t flush_bytes,
                                               unsigned long long *stamps, int *num_tiles);
 /* The single-RHS SpMV kernel instantiation launched for this matrix (tuning read once from
- * the MSPMV_SPMV_* environment; nontemporal matrix loads above 128 MiB), e.g.
+ * the MSPMV_SPMV_* environment; nontemporal matrix loads for a handle without a cache lease), e.g.
  * "k_spmv_tile<8,0,true>" -- the name rocprofv3 reports.  Valid until the next call on this
  * thread. */
 MSPMV_API const char *mspmv_spmv_kernel_name(mspmv_handle h);

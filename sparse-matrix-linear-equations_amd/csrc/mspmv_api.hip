@@ -84,6 +84,7 @@ static mspmv_status create_common(const mspmv_csr_d *a, int device, bool from_de
     h->m = a->num_rows;
     h->n = a->num_cols;
     h->nnz = a->num_nonzeros;
+    h->cache_ledger = !on_stream && !view_of;  // a sharded object's handles keep out of the ledger (cache_book)
     auto fail = [&](mspmv_status s) {
         mspmv_destroy(h);
         return s;
@@ -319,6 +320,7 @@ mspmv_status mspmv_destroy(mspmv_handle h)
     if (h->stream)
         (void)hipStreamSynchronize(h->stream);
     drop_plans(h);
+    cache_release(h);
     dev_free(h->d_row_offsets);
     if (h->own_arrays) {
         dev_free(h->d_cols);
@@ -460,6 +462,36 @@ mspmv_status mspmv_set_cu_limit(mspmv_handle h, int num_cus)
         const TilePlan *plan = nullptr;
         ST_TRY(solver_plan(h, 1, &plan));
         HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    return MSPMV_OK;
+}
+
+mspmv_status mspmv_set_cache_policy(mspmv_handle h, int policy)
+{
+    ST_TRY(check_handle(h));
+    if (policy != MSPMV_CACHE_AUTO && policy != MSPMV_CACHE_STREAM && policy != MSPMV_CACHE_RESIDENT)
+        return invalid("set_cache_policy: unknown policy");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->cache_policy = policy;
+    // a captured graph holds one instantiation of every product kernel
+    h->cg_graph.reset();
+    h->bicg_graph.reset();
+    h->pbicg_graph.reset();
+    h->bcg_graph.reset();
+    return cache_book(h, true);
+}
+
+mspmv_status mspmv_cache_info(mspmv_handle h, int *resident, long long *bytes)
+{
+    ST_TRY(check_handle(h));
+    if (resident)
+        *resident = h->cache_resident ? 1 : 0;
+    if (bytes) {
+        const TilePlan *plan = nullptr;
+        if (h->m > 0)
+            ST_TRY(product_plan(h, 1, &plan));
+        *bytes = plan ? plan->stream_bytes : 0;
     }
     return MSPMV_OK;
 }

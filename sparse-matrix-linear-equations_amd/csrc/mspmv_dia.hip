@@ -981,6 +981,10 @@ mspmv_status build_dia_plan(mspmv_handle_s *h, TilePlan &p, double min_fill, dou
     dd->rem = hp.rem;
     dd->rem_windows = hp.rem_windows;
     dd->fill = (double)(h->nnz - hp.rem) / (64.0 * (double)sumk);
+    // one product reads the value panels (1 KiB per offset pair), the headers, offsets and masks, and the
+    // remainder as a CSR of its own
+    p.stream_bytes = 1024 * sump + (long long)(16 * hdr.size() + 4 * offs.size() + 8 * masks.size()) +
+                     (hp.rem > 0 ? 12 * (long long)hp.rem + 4 * ((long long)m + 1) : 0);
     mspmv_status st;
     if ((st = dia_upload(&dd->d_hdr, hdr)) != MSPMV_OK || (st = dia_upload(&dd->d_off, offs)) != MSPMV_OK ||
         (st = dia_upload(&dd->d_mask, masks)) != MSPMV_OK)

@@ -232,6 +232,10 @@ struct TilePlan {
     int blk_two_rounds = 0;             // node-block tiles of more than one round of run slots (> kBlkTileChunks)
     std::vector<unsigned char> h_blk_reg;  // [num_tiles] 1: the plain SpMV reduces the tile in registers
                                            // (a reordered sum: mspmv_tile_modes reports 255)
+    // What one product on the plan streams from the matrix's own arrays, in bytes (x, y and solver vectors
+    // not counted): set where those arrays are allocated; the handle's cache lease is sized to the largest
+    // over its plans (cache_book).
+    long long stream_bytes = 0;
     SlabData *slab = nullptr;           // column-slab plan (tiles = blocks; mspmv_slab.hip), else null
     DiaData *dia = nullptr;             // offset-window plan (tiles = 64-row windows; mspmv_dia.hip), else null
 };
@@ -320,6 +324,16 @@ struct mspmv_handle_s {
     double *d_vals = nullptr;
     double setup_ms = 0.0;
     std::map<int, mspmv::TilePlan> plans;  // by nominal tile size
+    // Infinity-Cache lease (mspmv.h "Infinity-Cache leases"; the ledger: mspmv_cache.cpp; cache_book)
+    int cache_policy = MSPMV_CACHE_AUTO;
+    bool cache_resident = true;  // the products read the matrix with default-policy loads (else nontemporal)
+    long long cache_bytes = 0;   // the largest TilePlan::stream_bytes over `plans` when last booked
+    long long cache_lease = 0;   // bytes this handle holds in its device's ledger
+    size_t cache_plans = 0;      // plans.size() when last booked
+    // false: a sharded object's handle (created on its communicator's stream, or a row-range view of one, which
+    // reads its parent's arrays).  Under MSPMV_CACHE_AUTO it takes no lease and keeps the rule every handle had
+    // before the ledger (cache_book): nothing at N > 1 has been measured with leases.
+    bool cache_ledger = true;
     // CG workspace (grown on demand)
     size_t cg_cap_elems = 0;
     double *d_r = nullptr, *d_p0 = nullptr, *d_p1 = nullptr, *d_ap = nullptr;
@@ -683,7 +697,19 @@ hipError_t launch_stream_read(const double *p, size_t bytes, int num_cus, hipStr
 // The kernel launch_spmm_tile_only launches on `plan` at native width L, as rocprofv3 lists it (each kernel
 // family's name is formatted from the pick its launcher launches from; mspmv_*_kernel_name)
 std::string product_kernel_name(const mspmv_handle_s *h, const TilePlan &plan, int L);
-bool stream_nt(const mspmv_handle_s *h);
+// Nontemporal policy for the matrix stream, in every product kernel: the handle holds no Infinity-Cache lease
+// (cache_book), so its lines are not allowed to evict x / X or a resident matrix's.
+inline bool stream_nt(const mspmv_handle_s *h) { return !h->cache_resident; }
+// Books the handle's lease again when its set of plans changed (product_plan and solver_plan end with it) or
+// when `force` (mspmv_set_cache_policy): sized to the largest stream_bytes over the plans built, exchanged with
+// the device's ledger under the handle's policy.  When the load policy flips, the handle is synchronized and its
+// solver graphs dropped (a captured graph holds one instantiation).
+mspmv_status cache_book(mspmv_handle_s *h, bool force = false);
+// ... and returns it (mspmv_destroy)
+void cache_release(mspmv_handle_s *h);
+// Node-block record plan (k_spmv_blk): values + records + bounds and column bases.  Striped and pair tiles:
+// values + cols16 or cols + row ends + dictionary entries and indices (dict_entries: the tiles' distinct columns).
+long long tile_stream_bytes(const mspmv_handle_s *h, const TilePlan &p, long long dict_entries);
 
 // ---- runtime -> template dispatch ---------------------------------------------------
 // The native right-hand-side widths: every L-wide kernel is instantiated for exactly these.

@@ -2413,11 +2413,6 @@ static const Switches &switches()
     return w;
 }
 
-// Nontemporal policy for the matrix stream: a matrix larger than kNtBytes cannot stay in the
-// 256 MiB Infinity Cache across calls anyway, so its lines are not allowed to evict x / X.
-constexpr double kNtBytes = 128.0 * 1024 * 1024;
-bool stream_nt(const mspmv_handle_s *h) { return 12.0 * (double)h->nnz + 4.0 * (double)h->m > kNtBytes; }
-
 int spmv_items_per_thread() { return kSpmvIpt; }
 
 // SpMM tile depth: measured best 8 items per lane group for L <= 4 (fem-blocked pwtk shape,

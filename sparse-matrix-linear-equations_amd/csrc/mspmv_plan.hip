@@ -39,6 +39,8 @@ void mspmv::free_plan(TilePlan &p)
 // tile kernel can run on it.
 static mspmv_status build_plan(mspmv_handle_s *h, int L, const TilePlan **out, int lanes = 0,
                                const std::vector<int2> *fixed = nullptr);
+// product_plan before it books the handle's cache lease
+static mspmv_status product_plan_unbooked(mspmv_handle_s *h, int L, const TilePlan **out);
 
 // The in-tile reduction modes of a plan for L right-hand sides, built on first use.
 static mspmv_status ensure_modes(mspmv_handle_s *h, TilePlan &p, int L)
@@ -426,6 +428,7 @@ static mspmv_status build_plan(mspmv_handle_s *h, int L, const TilePlan **out, i
     // balanced plan (its kernel gathers x directly)
     const bool multi = !single;
     const bool want = fixed ? false : multi ? spmm_dict_max(L) > 0 : true;
+    long long dict_entries = 0;  // distinct columns over the tiles that gather through a dictionary
     if (T > 0 && h->nnz > 0 && want) {
         if ((st = dev_alloc(&p.d_dict, (size_t)h->nnz + kNnzPad)) != MSPMV_OK ||
             (st = dev_alloc(&p.d_ndict, (size_t)T)) != MSPMV_OK ||
@@ -445,8 +448,10 @@ static mspmv_status build_plan(mspmv_handle_s *h, int L, const TilePlan **out, i
             set_error(std::string("column dictionaries: ") + hipGetErrorString(e));
             return fail(MSPMV_ERR_HIP);
         }
-        for (int v : hnd)
+        for (int v : hnd) {
             p.num_tiles_dict += v > 0;
+            dict_entries += v;
+        }
         if (p.num_tiles_dict == 0) {  // no tile takes one: drop the arrays, the kernel skips the test
             dev_free(p.d_dict);
             dev_free(p.d_ndict);
@@ -456,6 +461,7 @@ static mspmv_status build_plan(mspmv_handle_s *h, int L, const TilePlan **out, i
             p.d_idx16 = nullptr;
         }
     }
+    p.stream_bytes = tile_stream_bytes(h, p, dict_entries);
     auto res = h->plans.emplace(fixed ? kRunPlanKey : p.lanes == 64 ? -tile : plan_key(L), p);  // one-wave: negative keys
     *out = &res.first->second;
     return MSPMV_OK;
@@ -721,10 +727,72 @@ mspmv_status mspmv::solver_plan(mspmv_handle_s *h, int L, const TilePlan **out)
     }
     ST_TRY(ensure_modes(h, *tp, L));
     *out = tp;
+    return cache_book(h);
+}
+
+long long mspmv::tile_stream_bytes(const mspmv_handle_s *h, const TilePlan &p, long long dict_entries)
+{
+    const long long nnz = h->nnz, T = p.num_tiles;
+    if (p.blk_spmv && p.d_recs)  // values, one 64-B record per descriptor slot, bounds (8 B) and column base per tile
+        return 8 * nnz + 4LL * kRecDwords * T * p.blk_stride + 12 * T;
+    const long long cols = p.d_cols16 && p.num_tiles16 == p.num_tiles ? 2 : 4;
+    // a dictionary tile reads its distinct columns and a 16-bit index per nonzero besides
+    const long long dict = p.d_dict ? 4 * dict_entries + 2 * nnz * p.num_tiles_dict / std::max(T, 1LL) : 0;
+    return (8 + cols) * nnz + 4 * ((long long)h->m + 1) + dict;
+}
+
+constexpr double kShardedNtBytes = 128.0 * 1024 * 1024;  // (cache_book: handles outside the ledger)
+
+mspmv_status mspmv::cache_book(mspmv_handle_s *h, bool force)
+{
+    if (!force && h->plans.size() == h->cache_plans)
+        return MSPMV_OK;
+    h->cache_plans = h->plans.size();
+    long long want = 0;
+    for (const auto &kv : h->plans)
+        want = std::max(want, kv.second.stream_bytes);
+    if (!force && want == h->cache_bytes)
+        return MSPMV_OK;
+    long long granted = 0;
+    int resident = 1;
+    if (!h->cache_ledger && h->cache_policy == MSPMV_CACHE_AUTO) {
+        // a sharded object's handle: any lease an override took goes back, and the matrix streams nontemporal when
+        // its CSR (12 B per nonzero + row offsets) is larger than half the 256 MiB cache, as before the ledger
+        ST_TRY(mspmv_cache_lease(h->device, h->cache_lease, 0, MSPMV_CACHE_STREAM, &granted, &resident));
+        resident = 12.0 * (double)h->nnz + 4.0 * (double)h->m > kShardedNtBytes ? 0 : 1;
+    } else {
+        ST_TRY(mspmv_cache_lease(h->device, h->cache_lease, want, h->cache_policy, &granted, &resident));
+    }
+    h->cache_bytes = want;
+    h->cache_lease = granted;
+    if ((resident != 0) != h->cache_resident) {
+        if (h->stream)
+            HIP_TRY(hipStreamSynchronize(h->stream));
+        h->cg_graph.reset();
+        h->bicg_graph.reset();
+        h->pbicg_graph.reset();
+        h->bcg_graph.reset();
+        h->cache_resident = resident != 0;
+    }
     return MSPMV_OK;
 }
 
+void mspmv::cache_release(mspmv_handle_s *h)
+{
+    long long granted = 0;
+    int resident = 0;
+    if (h->cache_lease > 0)
+        (void)mspmv_cache_lease(h->device, h->cache_lease, 0, MSPMV_CACHE_STREAM, &granted, &resident);
+    h->cache_lease = 0;
+}
+
 mspmv_status mspmv::product_plan(mspmv_handle_s *h, int L, const TilePlan **out)
+{
+    ST_TRY(product_plan_unbooked(h, L, out));
+    return cache_book(h);
+}
+
+static mspmv_status product_plan_unbooked(mspmv_handle_s *h, int L, const TilePlan **out)
 {
     PatternScope scope(h);  // the decisions share one host copy of the pattern
     ST_TRY(window_plan(h, L, out));

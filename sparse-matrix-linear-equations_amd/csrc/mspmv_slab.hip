@@ -929,6 +929,8 @@ static mspmv_status slab_finish(mspmv_handle_s *h, TilePlan &p, int cfg, int gro
     s->slots = oval.size();
     s->h_src.swap(osrc);
     p.slab = s;
+    // one product reads the value and column streams and every descriptor once
+    p.stream_bytes = (long long)(8 * oval.size() + 2 * ocol.size() + 16 * (dblk.size() + chunks.size()) + 8 * ents.size());
     mspmv_status st;
     if ((st = slab_upload(&s->d_blk, dblk)) != MSPMV_OK || (st = slab_upload(&s->d_chunk, chunks)) != MSPMV_OK ||
         (st = slab_upload(&s->d_ent, ents)) != MSPMV_OK || (st = slab_upload(&s->d_val, oval, kNnzPad)) != MSPMV_OK ||
@@ -1201,6 +1203,9 @@ static mspmv_status sell_finish(mspmv_handle_s *h, TilePlan &p, const std::vecto
         s->stats.add(MSPMV_SLAB_STAT_EMPTY_BLOCKS, o.segs.empty());
     }
     p.slab = s;
+    // one product reads the value slots, the column and run-word streams and every descriptor once
+    p.stream_bytes = (long long)(8 * val.size() + 2 * (col.size() + sents.size()) +
+                                 16 * (blk.size() + segs.size() + slices.size() + longs.size()));
     mspmv_status st;
     if ((st = slab_upload(&s->d_blk, blk)) != MSPMV_OK || (st = slab_upload(&s->d_chunk, segs)) != MSPMV_OK ||
         (st = slab_upload(&s->d_slice, slices)) != MSPMV_OK || (st = slab_upload(&s->d_sent, sents)) != MSPMV_OK ||
@@ -1918,6 +1923,7 @@ mspmv_status build_slab_mm_plan(mspmv_handle_s *h, int L, TilePlan &p)
         s->stats.add(MSPMV_SLAB_STAT_EMPTY_BLOCKS, o.chunks.empty());
     }
     p.slab = s;
+    p.stream_bytes = (long long)(8 * oval.size() + 2 * ocol.size() + 16 * (blk.size() + chunks.size()) + 8 * ents.size());
     if ((st = slab_upload(&s->d_blk, blk)) != MSPMV_OK || (st = slab_upload(&s->d_chunk, chunks)) != MSPMV_OK ||
         (st = slab_upload(&s->d_ent, ents)) != MSPMV_OK || (st = slab_upload(&s->d_val, oval, kNnzPad)) != MSPMV_OK ||
         (st = slab_upload(&s->d_col, ocol, kNnzPad)) != MSPMV_OK)

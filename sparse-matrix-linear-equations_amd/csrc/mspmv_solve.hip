@@ -360,6 +360,8 @@ static mspmv_status cg_solve_native(mspmv_handle_s *h, const double *d_b, double
     if (ic && ic->num_colors > 0)  // an apply is 2 C - 1 colour sweeps (mspmv_color.hip)
         h->last_cg_kernel = "MC-IC0-PCG (split, " + std::to_string(2 * ic->num_colors - 1) + " sweeps of " +
                             std::to_string(ic->num_colors) + " colours)";
+    if (stream_nt(h))  // the iteration's product kernels in their nontemporal instantiation (no cache lease)
+        h->last_cg_kernel += ", nontemporal matrix loads";
     const int saved_cap = h->hist_cap;
     h->hist_cap = use_cap;  // kernels record only what the caller asked for
     int poison = 0;

@@ -40,6 +40,7 @@ POISON_FILL, POISON_LATE_ZERO, POISON_NO_STOP = 1, 2, 4  # mspmv_test_poison_tic
 # CG calls return their status beside X: BREAKDOWN (4) is a per-column numerical event (the
 # frozen columns are reported, the others solved), so it is returned, not raised; everything
 # else -- STALL (8, an IC(0) triangular solve that never progressed) included -- raises.
+CACHE_AUTO, CACHE_STREAM, CACHE_RESIDENT = 0, 1, 2  # mspmv_set_cache_policy
 SUPPORTED_L = (1, 2, 4, 8, 16)  # native tile-kernel widths; SpMM and the CGs take any L >= 1
 # (column chunks / groups of these widths; the sharded CG and the timing helpers native only)
 
@@ -106,6 +107,12 @@ _SIGS = {
     "mspmv_test_poison_tickets": (_I, [_P, ctypes.c_uint, _I]),
     "mspmv_dist_test_poison_tickets": (_I, [_P, ctypes.c_uint, _I]),
     "mspmv_set_cu_limit": (_I, [_P, _I]),
+    "mspmv_set_cache_policy": (_I, [_P, _I]),
+    "mspmv_cache_info": (_I, [_P, _PI, ctypes.POINTER(ctypes.c_longlong)]),
+    "mspmv_cache_budget": (_I, [_I, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]),
+    "mspmv_cache_floor": (_I, [_I, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]),
+    "mspmv_cache_lease": (_I, [_I, ctypes.c_longlong, ctypes.c_longlong, _I, ctypes.POINTER(ctypes.c_longlong), _PI]),
+    "mspmv_cache_leased": (_I, [_I, ctypes.POINTER(ctypes.c_longlong)]),
     "mspmv_merge_coords": (_I, [_P, _I, ctypes.POINTER(Coord)]),
     "mspmv_dspmv": (_I, [_P, _P, _P]),
     "mspmv_dspmv_dev": (_I, [_P, _P, _P]),
@@ -563,6 +570,19 @@ class GpuCsr:
     def set_cu_limit(self, num_cus: int):
         """Run this handle's work on num_cus compute units (<= 0: all) -- mspmv_set_cu_limit."""
         _check(lib.mspmv_set_cu_limit(self.h, int(num_cus)), "set_cu_limit")
+
+    def set_cache_policy(self, policy: int):
+        """CACHE_RESIDENT: this matrix's arrays are read with default-policy loads and booked in the device's
+        Infinity-Cache ledger; CACHE_STREAM: nontemporal loads, no lease; CACHE_AUTO: the ledger decides
+        (mspmv_set_cache_policy).  Synchronizes the handle and drops its cached solver graphs."""
+        _check(lib.mspmv_set_cache_policy(self.h, int(policy)), "set_cache_policy")
+
+    def cache_info(self):
+        """(resident, bytes): whether the products read the matrix with default-policy loads, and what one plain
+        single-RHS product streams from the matrix's arrays on its plan (mspmv_cache_info)."""
+        r, b = ctypes.c_int(), ctypes.c_longlong()
+        _check(lib.mspmv_cache_info(self.h, ctypes.byref(r), ctypes.byref(b)), "cache_info")
+        return bool(r.value), b.value
 
     def merge_coords(self, num_parts: int) -> np.ndarray:
         out = (Coord * (num_parts + 1))()
@@ -1059,6 +1079,37 @@ def offset_windows(a: CsrMatrix, min_fill: float = 0.85, min_window_fill: float 
         return None
     return {"windows": nw.value, "sum_offsets": sk.value, "masked_windows": mw.value, "k": k[: nw.value],
             "remainder": rem.value}
+
+
+def cache_budget(device: int = 0, nbytes: int = -1) -> int:
+    """Sets the budget of the device's Infinity-Cache ledger in bytes (negative: query only) and returns the
+    value before the call (mspmv_cache_budget; host only)."""
+    old = ctypes.c_longlong()
+    _check(lib.mspmv_cache_budget(device, int(nbytes), ctypes.byref(old)), "cache_budget")
+    return old.value
+
+
+def cache_floor(device: int = 0, nbytes: int = -1) -> int:
+    """The same for the floor: a matrix stream of at most this many bytes keeps default-policy loads and books
+    nothing (mspmv_cache_floor; host only)."""
+    old = ctypes.c_longlong()
+    _check(lib.mspmv_cache_floor(device, int(nbytes), ctypes.byref(old)), "cache_floor")
+    return old.value
+
+
+def cache_lease(device: int, held: int, want: int, policy: int = CACHE_AUTO):
+    """The ledger's exchange a handle makes (mspmv_cache_lease; host only): (bytes booked, resident)."""
+    g, r = ctypes.c_longlong(), ctypes.c_int()
+    _check(lib.mspmv_cache_lease(device, int(held), int(want), int(policy), ctypes.byref(g), ctypes.byref(r)),
+           "cache_lease")
+    return g.value, bool(r.value)
+
+
+def cache_leased(device: int = 0) -> int:
+    """Sum of the live leases on the device's ledger (mspmv_cache_leased; host only)."""
+    b = ctypes.c_longlong()
+    _check(lib.mspmv_cache_leased(device, ctypes.byref(b)), "cache_leased")
+    return b.value
 
 
 def block_record_encode(offsets) -> tuple:
