@@ -215,8 +215,49 @@ MSPMV_API mspmv_status mspmv_spmm_batch_dev(int count, const mspmv_handle *hs, c
  * even after one reports): MSPMV_ERR_FAULT, naming the first such product, if a ticket fault was raised. */
 MSPMV_API mspmv_status mspmv_sync_batch(int count, const mspmv_handle *hs);
 
+/* ---- initial guess (warm start) and the true residual --------------------------------------- */
+/* Every solver below starts from x0 = 0 (the reference's behaviour, MSPMV_X0_ZERO, the default) unless the matrix's
+ * handle is set to MSPMV_X0_CALLER: then every solver called with `h` as the matrix reads X on entry as X0 -- the
+ * host- and device-pointer forms of mspmv_dcg_single, mspmv_dcg_multi, mspmv_dpcg_spai_multi, mspmv_dpcg_ic0_multi
+ * (natural and multi-colour factors), mspmv_dbicgstab_multi, mspmv_dpbicgstab_ilu0_multi and mspmv_dbcg_multi; the
+ * host-pointer forms upload X as well as B.  The setting is sticky on the handle, like mspmv_set_cu_limit and
+ * mspmv_set_cache_policy; *old (may be NULL) takes the mode before the call.  MSPMV_ERR_INVALID for a null handle
+ * or an unknown mode.  mspmv_dist_cg_dev (mspmv_dist.h) is out of scope: the sharded CG keeps x0 = 0.
+ * A warm solve is the cold recurrence continued from X0, with the stop test still relative to ||B||:
+ *   - R0 = B - A X0 (one product on the path the solver's own products take, one fused pass); the per-column
+ *     scalars start from R0.R0, and Z = M R, Rhat = P = R, H = R^T R follow on R0 unchanged;
+ *   - b_norm_j = ||B_j|| (0 -> 1): stop tests and history entries stay relative to ||B||; iterations count from
+ *     the warm start;
+ *   - entry test (warm only): a column with ||R0_j|| / b_norm_j < tolerance is marked converged by the init and
+ *     its X column is returned as given (every update of it is x + 0 p with p = 0, which keeps every value's bits but
+ *     a -0.0 entry's sign); when every column is, the solver returns *iters = 0 and MSPMV_OK and writes no history
+ *     entry.  (The cold path keeps the reference's behaviour, a zero column's
+ *     breakdown included.)
+ *   - a non-finite X0 or B: no new rule -- the column breaks down and freezes as a non-finite B does, X as given;
+ *   - block CG: its columns are coupled, so it needs a full-rank block of initial residuals: all columns converged
+ *     at entry returns 0 iterations and MSPMV_OK, otherwise a rank-deficient R0 (one exact column, say) is the
+ *     Cholesky-pivot MSPMV_ERR_BREAKDOWN at the init, X left as given;
+ *   - single-RHS CG runs the split iteration at L = 1 (the form MSPMV_CG_SPLIT=1 selects; mspmv_cg_kernel_name
+ *     reports it), not the resident or pipelined kernels, whose first iteration derives ||b|| from r.r;
+ *   - widths outside {1, 2, 4, 8, 16}: X0's columns travel with B's into each column group;
+ *   - X0 = 0 with tolerance < 1 and no zero column in B: X, *iters, the history and the status are bit for bit
+ *     the cold solve's (single-RHS: the cold split form's). */
+enum { MSPMV_X0_ZERO = 0, MSPMV_X0_CALLER = 1 };
+MSPMV_API mspmv_status mspmv_set_initial_guess(mspmv_handle h, int mode, int *old);
+/* R = B - A X on the handle's plain product, with its column norms from the same pass: norms[j] = ||B_j||_2 and
+ * norms[L + j] = ||R_j||_2 (2 L values, on the host).  Any L >= 1 (native widths 1, 2, 4, 8, 16; any other as
+ * column groups of those); square or rectangular handles: B and R are m x L, X is n x L, row-major.  d_R may be
+ * NULL when only the norms are wanted.  Synchronizes (the norms come back to the host) and checks the fault word
+ * as mspmv_dspmm does.  The check a caller makes of a solution: a solver's recurrence residual drifts from this
+ * one.  Device panels must be 16-byte aligned at the native widths.  mspmv_dresidual: host pointers. */
+MSPMV_API mspmv_status mspmv_dresidual_dev(mspmv_handle h, const double *d_B, const double *d_X, double *d_R, int L,
+                                           double *norms);
+MSPMV_API mspmv_status mspmv_dresidual(mspmv_handle h, const double *B, const double *X, double *R, int L,
+                                       double *norms);
+
 /* ---- CG ----------------------------------------------------------------------------- */
-/* Single-RHS CG, CGSolveSingle (work_2025/main/single_strategy.hpp:102-170): x0 = 0,
+/* Single-RHS CG, CGSolveSingle (work_2025/main/single_strategy.hpp:102-170): x0 = 0 (unless
+ * mspmv_set_initial_guess says MSPMV_X0_CALLER, above),
  * r = p = b; stop after the update of r when sqrt(r.r)/||b|| < tolerance, counting that
  * iteration; ||b|| == 0 -> 1.  `tolerance` has the reference's meaning (callers such as
  * cpu_singlecg.cpp:92,101 pass tol*||b||; that quirk is the caller's).  Returns the

@@ -454,6 +454,72 @@ int SPAISolveMultiple(Csr &a, Csr &m, const ValueT *B, ValueT *X, int num_vector
     return iters;
 }
 
+// ---- initial guess (warm start; no reference counterpart: every solver of the reference starts from 0) ----
+// While an InitialGuess(a) lives, every solver above called with `a` as the matrix reads X on entry as X0
+// (mspmv_set_initial_guess, MSPMV_X0_CALLER: stop test still relative to ||B||, iterations counted from X0, a column
+// already below the tolerance returned untouched); the handle's previous mode comes back when it goes.
+template <typename Csr>
+class InitialGuess {
+    mspmv_handle h_;
+    int old_ = MSPMV_X0_ZERO;
+
+public:
+    explicit InitialGuess(Csr &a) : h_(detail::handle_for(a))
+    {
+        detail::check(mspmv_set_initial_guess(h_, MSPMV_X0_CALLER, &old_), "mspmv_set_initial_guess");
+    }
+    ~InitialGuess() { (void)mspmv_set_initial_guess(h_, old_, nullptr); }
+    InitialGuess(const InitialGuess &) = delete;
+    InitialGuess &operator=(const InitialGuess &) = delete;
+};
+// ... or per call: the solvers' overloads that take the tag from_x after their reference arguments, e.g.
+//     CGSolveMultiple(a, B, X, L, max_iters, tol, NONZERO_SPLIT, mspmv_ref::from_x, &errs);
+struct from_x_t {};
+constexpr from_x_t from_x{};
+
+template <typename Csr, typename ValueT>
+int CGSolveSingle(Csr &a, const ValueT *b, ValueT *x, int max_iters, ValueT tolerance, from_x_t)
+{
+    InitialGuess<Csr> guess(a);
+    return CGSolveSingle(a, b, x, max_iters, tolerance);
+}
+template <typename Csr, typename ValueT, typename KernelT>
+int CGSolveMultiple(Csr &a, const ValueT *B, ValueT *X, int num_vectors, int max_iters, ValueT tolerance,
+                    KernelT kernel_type, from_x_t, std::vector<double> *max_errors = nullptr)
+{
+    InitialGuess<Csr> guess(a);
+    return CGSolveMultiple(a, B, X, num_vectors, max_iters, tolerance, kernel_type, max_errors);
+}
+template <typename Csr, typename ValueT>
+int BiCGStabSolveMultiple(Csr &a, const ValueT *B, ValueT *X, int num_vectors, int max_iters, ValueT tolerance,
+                          from_x_t, std::vector<double> *max_errors = nullptr)
+{
+    InitialGuess<Csr> guess(a);
+    return BiCGStabSolveMultiple(a, B, X, num_vectors, max_iters, tolerance, max_errors);
+}
+template <typename Csr, typename ValueT>
+int ILU0BiCGStabSolveMultiple(Csr &a, const ValueT *B, ValueT *X, int num_vectors, int max_iters, ValueT tolerance,
+                              from_x_t, std::vector<double> *max_errors = nullptr)
+{
+    InitialGuess<Csr> guess(a);
+    return ILU0BiCGStabSolveMultiple(a, B, X, num_vectors, max_iters, tolerance, max_errors);
+}
+template <typename Csr, typename ValueT, typename KernelT>
+int PCGSolveMultiple(Csr &a, const Csr &l, const Csr &l_transpose, const ValueT *B, ValueT *X, int num_vectors,
+                     int max_iters, ValueT tolerance, KernelT kernel_type, from_x_t,
+                     std::vector<double> *max_errors = nullptr)
+{
+    InitialGuess<Csr> guess(a);
+    return PCGSolveMultiple(a, l, l_transpose, B, X, num_vectors, max_iters, tolerance, kernel_type, max_errors);
+}
+template <typename Csr, typename ValueT, typename KernelT>
+int SPAISolveMultiple(Csr &a, Csr &m, const ValueT *B, ValueT *X, int num_vectors, int max_iters, ValueT tolerance,
+                      KernelT kernel_type, from_x_t, std::vector<double> *max_errors = nullptr)
+{
+    InitialGuess<Csr> guess(a);
+    return SPAISolveMultiple(a, m, B, X, num_vectors, max_iters, tolerance, kernel_type, max_errors);
+}
+
 // ---- the reference's timing harnesses --------------------------------------------------------
 // cpu_spmv.cpp:426-475.  Correctness call into vector_y_out (pre-filled with 0xff bytes, as the
 // reference's memset(-1)), then timing_iterations warm and timing_iterations timed SpMVs with x

@@ -89,7 +89,8 @@ MSPMV_API mspmv_status mspmv_dist_sync(mspmv_dist d);
 MSPMV_API mspmv_status mspmv_dist_time_local_dev(mspmv_dist d, double *d_Y_own, int L, int reps, double *avg_ms);
 /* Sharded CGSolveMultiple (collective): B_own / X_own are this rank's rows of the interleaved
  * n x L panels.  Iteration count, history and breakdown semantics as mspmv_dcg_multi, any L >= 1
- * (widths outside 1, 2, 4, 8, 16 as independent column groups, every rank the same groups). */
+ * (widths outside 1, 2, 4, 8, 16 as independent column groups, every rank the same groups).  Always
+ * from x0 = 0: the warm start of mspmv_set_initial_guess covers the single-GPU solvers only. */
 MSPMV_API mspmv_status mspmv_dist_cg_dev(mspmv_dist d, const double *d_B_own, double *d_X_own, int L,
                                          int max_iters, double tolerance, int *iters, double *max_err_hist,
                                          int hist_cap);

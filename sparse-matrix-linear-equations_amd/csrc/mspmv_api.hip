@@ -337,6 +337,8 @@ mspmv_status mspmv_destroy(mspmv_handle h)
     dev_free(h->d_scal);
     dev_free(h->d_bcg);
     dev_free(h->d_red);
+    dev_free(h->d_warm);
+    dev_free(h->d_resw);
     dev_free(h->d_conv);
     dev_free(h->d_ctrl);
     dev_free(h->d_hist);

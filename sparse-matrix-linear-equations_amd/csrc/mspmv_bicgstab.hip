@@ -35,6 +35,7 @@ struct BicgArgs {
     double *t;          // A s
     const double *hat;  // preconditioned only: Phat in the s pass, Shat in the update pass
     const double *b;    // init only
+    const double *bb_in;  // warm init only: [L] B_j.B_j (k_warm_residual)
     CgScalars *scal;
     CgControl *ctrl;
     unsigned char *conv;
@@ -109,7 +110,9 @@ __device__ __forceinline__ bool bicg_fold2(const BicgArgs &a, double2 acc0, doub
 }
 
 // X = 0, R = Rhat = P = B; rho_j = B_j.B_j, bnorm_j = sqrt of it (0 -> 1); scalars and control reset.
-template <int L>
+// WARM (k_cg_init's rule): X kept, a.b = a.r holds R0, so Rhat = P = R0 and rho_j = R0_j.R0_j; bnorm_j from bb_in;
+// the entry test.
+template <int L, bool WARM>
 __global__ __launch_bounds__(kBlock) void k_bicg_init(BicgArgs a)
 {
     constexpr int GL = L > 1 ? L / 2 : 1;
@@ -122,8 +125,10 @@ __global__ __launch_bounds__(kBlock) void k_bicg_init(BicgArgs a)
     double2 acc = make_double2(0.0, 0.0);
     for_pairs<GL>(npairs, 0, [&](long long i) {
         const double2 b = reinterpret_cast<const double2 *>(a.b)[i];
-        reinterpret_cast<double2 *>(a.x)[i] = make_double2(0.0, 0.0);
-        reinterpret_cast<double2 *>(a.r)[i] = b;
+        if (!WARM) {
+            reinterpret_cast<double2 *>(a.x)[i] = make_double2(0.0, 0.0);
+            reinterpret_cast<double2 *>(a.r)[i] = b;
+        }
         reinterpret_cast<double2 *>(a.rhat)[i] = b;
         reinterpret_cast<double2 *>(a.p)[i] = b;
         acc.x += b.x * b.x;
@@ -132,8 +137,10 @@ __global__ __launch_bounds__(kBlock) void k_bicg_init(BicgArgs a)
     if ((a.n_elems & 1) && blockIdx.x == 0 && tid == 0) {  // L == 1 with odd n
         const long long i = a.n_elems - 1;
         const double b = a.b[i];
-        a.x[i] = 0.0;
-        a.r[i] = b;
+        if (!WARM) {
+            a.x[i] = 0.0;
+            a.r[i] = b;
+        }
         a.rhat[i] = b;
         a.p[i] = b;
         acc.x += b * b;
@@ -144,7 +151,7 @@ __global__ __launch_bounds__(kBlock) void k_bicg_init(BicgArgs a)
     if (tid < L) {
         CgScalars &s = a.scal[tid];
         const double bb = s_out[tid];
-        const double bn = sqrt(bb);
+        const double bn = sqrt(WARM ? a.bb_in[tid] : bb);
         s.rho = bb;
         s.rs_old = bb;
         s.b_norm = bn == 0.0 ? 1.0 : bn;
@@ -153,11 +160,17 @@ __global__ __launch_bounds__(kBlock) void k_bicg_init(BicgArgs a)
         s.omega = 0.0;
         s.pAp = 0.0;
         s.rs_new = 0.0;
-        a.conv[tid] = 0;
+        a.conv[tid] = WARM && sqrt(bb) / s.b_norm < a.tol ? 1 : 0;  // a NaN ratio: not converged
     }
+    if (WARM)
+        __syncthreads();
     if (tid == 0) {
+        int nconv = 0;
+        if (WARM)
+            for (int j = 0; j < L; ++j)
+                nconv += a.conv[j] != 0;
         a.ctrl->iter = 0;
-        a.ctrl->done = 0;
+        a.ctrl->done = WARM && nconv == L;
         a.ctrl->iters_out = 0;
         a.ctrl->breakdown = 0;
     }
@@ -429,12 +442,18 @@ static BicgArgs bicg_args(mspmv_handle_s *h, double *d_x, int L, double tol)
     return a;
 }
 
-hipError_t launch_bicgstab_init(mspmv_handle_s *h, const double *d_b, double *d_x, int L, double tol, int nblk)
+hipError_t launch_bicgstab_init(mspmv_handle_s *h, const double *d_b, double *d_x, int L, double tol, int nblk,
+                                bool warm)
 {
     BicgArgs a = bicg_args(h, d_x, L, tol);
-    a.b = d_b;
+    a.b = warm ? h->d_r : d_b;
+    a.bb_in = warm ? h->d_warm : nullptr;
     return dispatch_L(L, [&](auto Lc) {
-        hipLaunchKernelGGL((k_bicg_init<decltype(Lc)::value>), dim3(nblk), dim3(kBlock), 0, h->stream, a);
+        constexpr int LL = decltype(Lc)::value;
+        if (warm)
+            hipLaunchKernelGGL((k_bicg_init<LL, true>), dim3(nblk), dim3(kBlock), 0, h->stream, a);
+        else
+            hipLaunchKernelGGL((k_bicg_init<LL, false>), dim3(nblk), dim3(kBlock), 0, h->stream, a);
         return hipGetLastError();
     });
 }

@@ -47,6 +47,7 @@ struct BcgArgs {
     double *s;          // the search directions S
     const double *q;    // A S
     const double *b;    // init only
+    const double *bb_in;  // warm init only: [2 L] B_j.B_j, then R0_j.R0_j (k_warm_residual)
     double *small;      // the small matrices (bcg_small_*), written by the folds' last blocks
     CgControl *ctrl;
     double *partials;   // [blocks][L^2] and the fold's levels
@@ -257,7 +258,12 @@ __device__ __forceinline__ void bcg_store_dir(const BcgArgs &a, const double *s_
 
 // X = 0, W = B (raw; k_bcg_dir<L, true> scales it), H = B^T B.  The last block: zeta = chol(H), C = zeta, bnorm, the
 // control word reset.  A pivot failure (a zero or dependent right-hand-side column) ends the solve here, X = 0.
-template <int L>
+// WARM (mspmv_set_initial_guess): X kept, a.b = a.w holds R0 = B - A X0 (raw), so H = R0^T R0 and C = chol(H).
+// Before the factor, the entry test on H's diagonal: every sqrt(H_jj) / ||B_j|| < tol ends the solve with 0
+// iterations and no breakdown; otherwise a rank-deficient R0 (an exact column) is the pivot failure above, X as
+// given.  bnorm_j = ||C e_j|| (||B_j|| / ||R0_j||), the ratio from k_warm_residual's two sums, which run in one
+// order: with X0 = 0 they are equal, the ratio is exactly 1 and bnorm_j has the cold init's bits.
+template <int L, bool WARM>
 __global__ __launch_bounds__(kBlock) void k_bcg_init(BcgArgs a)
 {
     constexpr int GL = L > 1 ? L / 2 : 1;
@@ -274,19 +280,43 @@ __global__ __launch_bounds__(kBlock) void k_bcg_init(BcgArgs a)
         acc[k] = make_double2(0.0, 0.0);
     for_pairs<GL>(a.n_elems / 2, 0, [&](long long i) {
         const double2 b = reinterpret_cast<const double2 *>(a.b)[i];
-        reinterpret_cast<double2 *>(a.x)[i] = make_double2(0.0, 0.0);
-        reinterpret_cast<double2 *>(a.w)[i] = b;
+        if (!WARM) {
+            reinterpret_cast<double2 *>(a.x)[i] = make_double2(0.0, 0.0);
+            reinterpret_cast<double2 *>(a.w)[i] = b;
+        }
         bcg_gram_add<L>(b, b, acc);
     });
     if ((a.n_elems & 1) && blockIdx.x == 0 && tid == 0) {  // L == 1 with odd n
         const long long i = a.n_elems - 1;
         const double b = a.b[i];
-        a.x[i] = 0.0;
-        a.w[i] = b;
+        if (!WARM) {
+            a.x[i] = 0.0;
+            a.w[i] = b;
+        }
         acc[0].x += b * b;
     }
     if (!bcg_fold<L>(a, acc, s_g, s_colred, s_out, &s_last))
         return;
+    if (WARM) {
+        if (tid < L) {
+            const double bn = sqrt(a.bb_in[tid]);
+            s_col[tid] = sqrt(s_out[tid * L + tid]) / (bn == 0.0 ? 1.0 : bn);
+        }
+        __syncthreads();
+        bool all = true;
+        for (int j = 0; j < L; ++j)
+            all = all && s_col[j] < a.tol;  // a NaN ratio: not converged
+        if (all) {
+            if (tid == 0) {
+                a.ctrl->iter = 0;
+                a.ctrl->iters_out = 0;
+                a.ctrl->done = 1;
+                a.ctrl->breakdown = 0;
+            }
+            return;
+        }
+        __syncthreads();  // bcg_chol reuses s_col
+    }
     const int piv = bcg_chol<L>(s_out, s_col, &s_piv);
     if (tid == 0) {
         a.ctrl->iter = 0;
@@ -302,7 +332,9 @@ __global__ __launch_bounds__(kBlock) void k_bcg_init(BcgArgs a)
         double s = s_out[tid] * s_out[tid];
         for (int p = 1; p < L; ++p)
             s += s_out[p * L + tid] * s_out[p * L + tid];
-        const double bn = sqrt(s);
+        double bn = sqrt(s);
+        if (WARM)
+            bn = bn * (sqrt(a.bb_in[tid]) / sqrt(a.bb_in[L + tid]));
         bcg_small<L>(a, kBcgMats)[tid] = bn == 0.0 ? 1.0 : bn;
     }
     bcg_store_dir<L>(a, s_out, s_m);
@@ -507,13 +539,17 @@ static BcgArgs bcg_args(mspmv_handle_s *h, double *d_x, int L, double tol)
     return a;
 }
 
-hipError_t launch_bcg_init(mspmv_handle_s *h, const double *d_b, double *d_x, int L, double tol, int nblk)
+hipError_t launch_bcg_init(mspmv_handle_s *h, const double *d_b, double *d_x, int L, double tol, int nblk, bool warm)
 {
     BcgArgs a = bcg_args(h, d_x, L, tol);
-    a.b = d_b;
+    a.b = warm ? h->d_r : d_b;
+    a.bb_in = warm ? h->d_warm : nullptr;
     return dispatch_L(L, [&](auto Lc) {
         constexpr int LL = decltype(Lc)::value;
-        hipLaunchKernelGGL((k_bcg_init<LL>), dim3(nblk), dim3(kBlock), 0, h->stream, a);
+        if (warm)
+            hipLaunchKernelGGL((k_bcg_init<LL, true>), dim3(nblk), dim3(kBlock), 0, h->stream, a);
+        else
+            hipLaunchKernelGGL((k_bcg_init<LL, false>), dim3(nblk), dim3(kBlock), 0, h->stream, a);
         hipLaunchKernelGGL((k_bcg_dir<LL, true>), dim3(nblk), dim3(kBlock), 0, h->stream, a);
         return hipGetLastError();
     });

@@ -111,7 +111,11 @@ __global__ __launch_bounds__(kBlock) void k_fold_dot(const double *part, int T, 
 
 // x = 0, r = p0 = b; rs_old_j = r_j.r_j, b_norm_j = sqrt(b_j.b_j) (no_pretreatment.hpp:61-79,
 // single_strategy.hpp:120-131).
-template <int L>
+// WARM (mspmv_set_initial_guess): x is kept and a.p = a.r holds R0 = B - A X0 (k_warm_residual), taken where the
+// cold init takes b -- same grid, sweep and fold, so R0.R0 has the cold B.B's bits when X0 = 0; b_norm_j comes from
+// bb_in (B_j.B_j, folded in this fold's order); a column with sqrt(R0_j.R0_j) / b_norm_j < tol starts converged,
+// and all of them end the solve here with 0 iterations.
+template <int L, bool WARM = false>
 __global__ __launch_bounds__(kBlock) void k_cg_init(CgVecArgs a)
 {
     constexpr int GL = L > 1 ? L / 2 : 1;
@@ -125,8 +129,10 @@ __global__ __launch_bounds__(kBlock) void k_cg_init(CgVecArgs a)
     double2 acc = make_double2(0.0, 0.0);
     for (long long i = (long long)blockIdx.x * kBlock + tid; i < npairs; i += stride) {
         const double2 b = reinterpret_cast<const double2 *>(a.p)[i];
-        reinterpret_cast<double2 *>(a.x)[i] = make_double2(0.0, 0.0);
-        reinterpret_cast<double2 *>(a.r)[i] = b;
+        if (!WARM) {
+            reinterpret_cast<double2 *>(a.x)[i] = make_double2(0.0, 0.0);
+            reinterpret_cast<double2 *>(a.r)[i] = b;
+        }
         reinterpret_cast<double2 *>(a.p0)[i] = b;
         acc.x += b.x * b.x;
         acc.y += b.y * b.y;
@@ -134,8 +140,10 @@ __global__ __launch_bounds__(kBlock) void k_cg_init(CgVecArgs a)
     if ((a.n_elems & 1) && blockIdx.x == 0 && tid == 0) {  // L == 1 with odd n
         const long long i = a.n_elems - 1;
         const double b = a.p[i];
-        a.x[i] = 0.0;
-        a.r[i] = b;
+        if (!WARM) {
+            a.x[i] = 0.0;
+            a.r[i] = b;
+        }
         a.p0[i] = b;
         acc.x += b * b;
     }
@@ -150,17 +158,23 @@ __global__ __launch_bounds__(kBlock) void k_cg_init(CgVecArgs a)
             CgScalars &s = a.scal[tid];
             const double bb = s_out[tid];
             s.rs_old = bb;
-            double bn = sqrt(bb);
+            double bn = sqrt(WARM ? a.bb_in[tid] : bb);
             s.b_norm = bn == 0.0 ? 1.0 : bn;
             s.alpha = 0.0;
             s.beta = 0.0;
             s.pAp = 0.0;
             s.rs_new = 0.0;
-            a.conv[tid] = 0;
+            a.conv[tid] = WARM && sqrt(bb) / s.b_norm < a.tol ? 1 : 0;  // a NaN ratio: not converged
         }
+        if (WARM)
+            __syncthreads();
         if (tid == 0) {
+            int nconv = 0;
+            if (WARM)
+                for (int j = 0; j < L; ++j)
+                    nconv += a.conv[j] != 0;
             a.ctrl->iter = 0;
-            a.ctrl->done = 0;
+            a.ctrl->done = WARM && nconv == L;
             a.ctrl->iters_out = 0;
             a.ctrl->breakdown = 0;
         }
@@ -565,11 +579,12 @@ static CgVecArgs cg_vec_args(mspmv_handle_s *h, double *d_x, int L, double tol)
     return va;
 }
 
-hipError_t launch_cg_init(mspmv_handle_s *h, const double *d_b, double *d_x, int L, double tol, int nblk)
+hipError_t launch_cg_init(mspmv_handle_s *h, const double *d_b, double *d_x, int L, double tol, int nblk, bool warm)
 {
     CgVecArgs a = cg_vec_args(h, d_x, L, tol);
-    a.p = d_b;
-    return launch_dist_vec(CgVecPass::InitPartials, a, L, nblk, nullptr, h->stream);
+    a.p = warm ? h->d_r : d_b;
+    a.bb_in = warm ? h->d_warm : nullptr;
+    return launch_dist_vec(warm ? CgVecPass::InitWarm : CgVecPass::InitPartials, a, L, nblk, nullptr, h->stream);
 }
 
 // ---- pipelined single-RHS CG (consumer-side reductions, no ticket chains) -------------------
@@ -868,9 +883,9 @@ bool cg_split_iteration(int L)
 }
 
 hipError_t launch_cg_iteration(mspmv_handle_s *h, const TilePlan &plan, const TilePlan *splan, bool dot_fused,
-                               double *d_x, int L, int parity, int nblk, double tol)
+                               double *d_x, int L, int parity, int nblk, double tol, bool split)
 {
-    if (cg_split_iteration(L))
+    if (split)
         return launch_cg_iteration_split(h, plan, splan, dot_fused, d_x, L, nblk, tol);
     double *rp_old = parity ? h->d_p1 : h->d_p0;  // {r_k, p_{k-1}} interleaved (cg_rp)
     double *rp_new = parity ? h->d_p0 : h->d_p1;  // receives p_k, then r_{k+1}
@@ -902,6 +917,7 @@ static hipError_t dist_launch_L(CgVecPass pass, const CgVecArgs &a, int nblk, do
 {
     switch (pass) {
     case CgVecPass::InitPartials: hipLaunchKernelGGL((k_cg_init<L>), dim3(nblk), dim3(kBlock), 0, s, a); break;
+    case CgVecPass::InitWarm: hipLaunchKernelGGL((k_cg_init<L, true>), dim3(nblk), dim3(kBlock), 0, s, a); break;
     case CgVecPass::InitFinish: hipLaunchKernelGGL((k_dist_init_finish<L>), dim3(1), dim3(64), 0, s, a); break;
     case CgVecPass::PUpdate: hipLaunchKernelGGL((k_dist_pupdate<L>), dim3(nblk), dim3(kBlock), 0, s, a, p); break;
     case CgVecPass::XrUpdate: hipLaunchKernelGGL((k_cg_update<L>), dim3(nblk), dim3(kBlock), 0, s, a); break;
@@ -969,9 +985,9 @@ static CgVecArgs pcg_vec_args(mspmv_handle_s *h, double *d_x, int L, double tol)
 // X = 0, R = B, b_norms (sparse_approximate_inverse.hpp:59-78); Z = M R and rs_old = R.Z
 // (:80-92, :99-100); P = Z (:94-97).  Z lives in h->d_p1, P in h->d_p0.
 hipError_t launch_pcg_init(mspmv_handle_s *h, mspmv_handle_s *hm, const TilePlan &mplan, const double *d_b,
-                           double *d_x, int L, double tol, int nblk)
+                           double *d_x, int L, double tol, int nblk, bool warm)
 {
-    hipError_t e = launch_cg_init(h, d_b, d_x, L, tol, nblk);
+    hipError_t e = launch_cg_init(h, d_b, d_x, L, tol, nblk, warm);
     if (e != hipSuccess)
         return e;
     hipStream_t own = hm->stream;
@@ -1013,9 +1029,9 @@ hipError_t launch_pcg_iteration(mspmv_handle_s *h, mspmv_handle_s *hm, const Til
 // X = 0, R = B, b_norms (incomplete_cholesky.hpp:66-85); Z = M^-1 R (:87-92); P = Z (:94-95);
 // rs_old = R.Z (:97).  Z lives in h->d_p1, P in h->d_p0.
 hipError_t launch_pcg_ic0_init(mspmv_handle_s *h, mspmv_ic0_s *ic, const double *d_b, double *d_x, int L, double tol,
-                               int nblk)
+                               int nblk, bool warm)
 {
-    hipError_t e = launch_cg_init(h, d_b, d_x, L, tol, nblk);
+    hipError_t e = launch_cg_init(h, d_b, d_x, L, tol, nblk, warm);
     if (e == hipSuccess)
         e = tri_apply(ic, h->d_r, h->d_p1, L, h->d_ctrl, h->stream);
     CgVecArgs va = pcg_vec_args(h, d_x, L, tol);

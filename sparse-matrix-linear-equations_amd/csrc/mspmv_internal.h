@@ -349,6 +349,12 @@ struct mspmv_handle_s {
     // last blocks (kBcgSmallDoubles; allocated by that solver only)
     double *d_bcg = nullptr;
     double *d_red = nullptr;  // [L] p.Ap of the split multi-RHS iteration (k_spmm_tile MODE 2 -> k_cg_update)
+    // warm start (mspmv_set_initial_guess; mspmv_warm.hip): MSPMV_X0_* -- every solver called with this handle as
+    // the matrix reads X on entry as X0 -- and the pass's column sums [2 x 16]: B_j.B_j, then R0_j.R0_j
+    int x0_mode = MSPMV_X0_ZERO;
+    double *d_warm = nullptr;
+    double *d_resw = nullptr;  // mspmv_dresidual_dev's product panel A X (m x w), its only vector
+    size_t resw_cap = 0;
     unsigned char *d_conv = nullptr;   // per-column converged flags
     mspmv::CgControl *d_ctrl = nullptr;
     mspmv::CgControl *h_ctrl = nullptr;  // pinned mirror
@@ -742,15 +748,23 @@ inline auto dispatch_bool(bool flag, F &&f)
 }
 
 // CG pieces (mspmv_cg_passes.hip, but for the stamped SpMV and the dot-mode tiles)
-hipError_t launch_cg_init(mspmv_handle_s *h, const double *d_b, double *d_x, int L, double tol, int nblk);
+// warm (every init below; mspmv_warm.hip): the caller ran launch_warm_residual first -- R0 = B - A X0 sits in
+// h->d_r and is taken where the cold init takes d_b, X is kept, b_norm comes from the B.B in h->d_warm, and a column
+// with ||R0_j|| / b_norm_j < tol starts converged (all of them: done, 0 iterations).
+hipError_t launch_cg_init(mspmv_handle_s *h, const double *d_b, double *d_x, int L, double tol, int nblk,
+                          bool warm = false);
+// R = B - W (W = A X, in memory) with B_j.B_j and R_j.R_j into h->d_warm [2 L] (k_warm_residual): nblk blocks, the
+// handle's partials (rows 2 L wide) and zeroed tickets; d_R null: the sums alone.
+hipError_t launch_warm_residual(mspmv_handle_s *h, const double *d_B, const double *d_W, double *d_R, int L, int nblk);
 // Diagnostic: the plain SpMV's k_spmv_tile in its stamped instantiation (hipErrorNotSupported for plans
 // that run another kernel); d_stamps [num_tiles][6] (mspmv_spmv_tile_stamps)
 hipError_t launch_spmv_tile_stamped(mspmv_handle_s *h, const TilePlan &plan, const double *d_x, double *d_y,
                                    unsigned long long *d_stamps);
 // splan / dot_fused: the split iteration's plain-product plan and window dot mode, resolved once per
-// solve by cg_solve_native (launch_cg_iteration_split)
+// solve by cg_solve_native (launch_cg_iteration_split); split: the split iteration (cg_split_iteration(L), or a
+// warm single-RHS solve), else the pipelined single-RHS one
 hipError_t launch_cg_iteration(mspmv_handle_s *h, const TilePlan &plan, const TilePlan *splan, bool dot_fused,
-                               double *d_x, int L, int parity, int nblk, double tol);
+                               double *d_x, int L, int parity, int nblk, double tol, bool split);
 int cg_update_blocks(long long elems, int num_cus);
 // The plain L-wide product of a solver's iteration on the solve's plan (splan: offset windows or column slabs,
 // else null -> the merge tiles of plan), stopped by the handle's control word
@@ -761,7 +775,8 @@ std::string solver_product_name(const mspmv_handle_s *h, const TilePlan &plan, c
 // BiCGSTAB (mspmv_bicgstab.hip): init (X = 0, R = Rhat = P = B, rho = B.B) and one iteration -- V = A P, the
 // rhat.v pass, the s pass, T = A s, the t.t / t.s pass, the update pass (stop test, beta), the p pass.  R, P, V,
 // T live in h->d_r, d_p0, d_ap, d_p1; Rhat in h->d_rhat.  Partial rows are 2 L wide.
-hipError_t launch_bicgstab_init(mspmv_handle_s *h, const double *d_b, double *d_x, int L, double tol, int nblk);
+hipError_t launch_bicgstab_init(mspmv_handle_s *h, const double *d_b, double *d_x, int L, double tol, int nblk,
+                                bool warm = false);
 hipError_t launch_bicgstab_iteration(mspmv_handle_s *h, const TilePlan &plan, const TilePlan *splan, double *d_x, int L,
                                      int nblk, double tol);
 // The same right-preconditioned with M = L U (ilu: the factor): Phat = U^-1 L^-1 P before the first product,
@@ -776,7 +791,8 @@ hipError_t launch_pbicgstab_iteration(mspmv_handle_s *h, mspmv_ilu0_s *ilu, cons
 constexpr int kBcgSmallDoubles = 5 * 16 * 16 + 16;
 constexpr int kBcgBroke = 0x100;
 constexpr int kBcgBrokeG = 0x10;
-hipError_t launch_bcg_init(mspmv_handle_s *h, const double *d_b, double *d_x, int L, double tol, int nblk);
+hipError_t launch_bcg_init(mspmv_handle_s *h, const double *d_b, double *d_x, int L, double tol, int nblk,
+                           bool warm = false);
 hipError_t launch_bcg_iteration(mspmv_handle_s *h, const TilePlan &plan, const TilePlan *splan, double *d_x, int L,
                                 int nblk, double tol);
 // Iterations per CG batch / graph replay for an m-row, nnz-nonzero matrix and L columns.
@@ -850,6 +866,7 @@ struct CgVecArgs {
     // first (rev = 1) or first to last, alternately, so a pass starts on the lines the previous
     // pass touched last -- still in the 256 MiB Infinity Cache (every lane keeps its column pair).
     int rev;
+    const double *bb_in;  // warm init (k_cg_init<L, true>): [L] B_j.B_j from k_warm_residual
     // Cache policy of the split CG's passes (the 256 MiB Infinity Cache holds about one L = 8 vector
     // of the nlpkkt120 size): a vector read for the last time before another pass streams over it is
     // loaded nontemporal -- Ap in the r update, p in the p.Ap pass (next read by the p update, two
@@ -860,6 +877,7 @@ struct CgVecArgs {
 // The vector passes launch_dist_vec runs on a CgVecArgs.
 enum class CgVecPass {
     InitPartials,  // k_cg_init: x = 0, r = p0 = b, b.b partial sums -> red_out
+    InitWarm,      // k_cg_init<L, true>: x kept, p0 = r = R0 (in a.r), R0.R0, b_norm from bb_in, the entry test
     InitFinish,    // k_dist_init_finish: scalars from red_in = all-reduced b.b
     PUpdate,       // k_dist_pupdate: p = r + beta p (p: the `p` argument)
     XrUpdate,      // k_cg_update: x, r (alpha from red_in = all-reduced p.Ap when set; r.r -> red_out)
@@ -915,13 +933,13 @@ mspmv_status time_spmm_batch(int count, const mspmv_handle *hs, const double *co
 // (X = 0, R = B, Z = M R, P = Z, rs_old = R.Z) and one iteration (AP = A P -> alpha; X, R update
 // and stop test; Z = M R -> beta; P = Z + beta P).  hm's SpMMs run on h's stream.
 hipError_t launch_pcg_init(mspmv_handle_s *h, mspmv_handle_s *hm, const TilePlan &mplan, const double *d_b,
-                           double *d_x, int L, double tol, int nblk);
+                           double *d_x, int L, double tol, int nblk, bool warm = false);
 hipError_t launch_pcg_iteration(mspmv_handle_s *h, mspmv_handle_s *hm, const TilePlan &plan, const TilePlan &mplan,
                                 double *d_x, int L, int nblk, double tol);
 // IC(0)-preconditioned block CG (PCGSolveMultiple, work_2025/main/incomplete_cholesky.hpp:33-199):
 // Z = L^-T L^-1 R by tri_apply; ic->d_y must hold m * L.
 hipError_t launch_pcg_ic0_init(mspmv_handle_s *h, mspmv_ic0_s *ic, const double *d_b, double *d_x, int L, double tol,
-                               int nblk);
+                               int nblk, bool warm = false);
 hipError_t launch_pcg_ic0_iteration(mspmv_handle_s *h, mspmv_ic0_s *ic, const TilePlan &plan, double *d_x, int L,
                                     int nblk, double tol);
 // Partials capacity (doubles) and group-ticket count for `slots` partial slots of L columns.

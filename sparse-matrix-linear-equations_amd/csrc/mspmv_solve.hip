@@ -17,6 +17,33 @@ using namespace mspmv;
 // ---- the workspace -------------------------------------------------------------------------
 // fold_width: columns of a partial row when wider than L (BiCGSTAB's two-dot folds: 2 L; the block CG's Gram
 // folds: L^2)
+// The folds' share of it: partial rows of `width` columns for `slots` slots, their tickets (zeroed when allocated),
+// the control word and the warm pass's sums -- all a fold outside a solve needs (mspmv_dresidual_dev).
+static mspmv_status ensure_fold_workspace(mspmv_handle_s *h, size_t slots, int width)
+{
+    const size_t pcap = partials_capacity(slots, width);
+    if (pcap > h->partials_cap) {
+        dev_free(h->d_partials);
+        h->partials_cap = 0;
+        ST_TRY(dev_alloc(&h->d_partials, pcap));
+        h->partials_cap = pcap;
+    }
+    if (gtickets_capacity(slots) > h->gtickets_cap) {
+        dev_free(h->d_gtickets);
+        h->gtickets_cap = 0;
+        ST_TRY(dev_alloc(&h->d_gtickets, gtickets_capacity(slots)));
+        // on the handle's stream: it is non-blocking, so a null-stream memset is not ordered before the
+        // folds queued on it next
+        HIP_TRY(hipMemsetAsync(h->d_gtickets, 0, sizeof(unsigned) * gtickets_capacity(slots), h->stream));
+        h->gtickets_cap = gtickets_capacity(slots);
+    }
+    if (!h->d_ctrl)
+        ST_TRY(dev_alloc(&h->d_ctrl, 1));
+    if (!h->d_warm)
+        ST_TRY(dev_alloc(&h->d_warm, (size_t)2 * 16));
+    return MSPMV_OK;
+}
+
 static mspmv_status ensure_cg_workspace(mspmv_handle_s *h, int L, int nblk, int num_tiles, int hist_cap,
                                         int fold_width = 0)
 {
@@ -34,25 +61,9 @@ static mspmv_status ensure_cg_workspace(mspmv_handle_s *h, int L, int nblk, int 
         ST_TRY(dev_alloc(&h->d_ap, elems));
         h->cg_cap_elems = elems;
     }
-    const size_t slots = (size_t)std::max(nblk, num_tiles);
-    const size_t pcap = partials_capacity(slots, std::max(L, fold_width));
-    if (pcap > h->partials_cap) {
-        dev_free(h->d_partials);
-        h->partials_cap = 0;
-        ST_TRY(dev_alloc(&h->d_partials, pcap));
-        h->partials_cap = pcap;
-    }
+    ST_TRY(ensure_fold_workspace(h, (size_t)std::max(nblk, num_tiles), std::max(L, fold_width)));
     if (!h->d_partials_b)
         ST_TRY(dev_alloc(&h->d_partials_b, (size_t)kUpdateMaxBlocks));
-    if (gtickets_capacity(slots) > h->gtickets_cap) {
-        dev_free(h->d_gtickets);
-        h->gtickets_cap = 0;
-        ST_TRY(dev_alloc(&h->d_gtickets, gtickets_capacity(slots)));
-        // on the handle's stream: it is non-blocking, so a null-stream memset is not ordered before the
-        // folds queued on it next
-        HIP_TRY(hipMemsetAsync(h->d_gtickets, 0, sizeof(unsigned) * gtickets_capacity(slots), h->stream));
-        h->gtickets_cap = gtickets_capacity(slots);
-    }
     if (L > h->scal_cap) {
         dev_free(h->d_scal);
         dev_free(h->d_conv);
@@ -63,8 +74,6 @@ static mspmv_status ensure_cg_workspace(mspmv_handle_s *h, int L, int nblk, int 
         ST_TRY(dev_alloc(&h->d_red, (size_t)L));
         h->scal_cap = L;
     }
-    if (!h->d_ctrl)
-        ST_TRY(dev_alloc(&h->d_ctrl, 1));
     if (!h->h_ctrl)
         HIP_TRY(hipHostMalloc((void **)&h->h_ctrl, sizeof(CgControl) * 2, hipHostMallocDefault));
     if (hist_cap > h->hist_cap) {
@@ -161,6 +170,17 @@ static mspmv_status solve_poison_fill(mspmv_handle_s *h, int poison)
     if (poison & MSPMV_POISON_FILL)
         HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)h->d_gtickets, (int)h->poison_value, h->gtickets_cap, h->stream));
     return MSPMV_OK;
+}
+
+// Warm start (mspmv_set_initial_guess, MSPMV_X0_CALLER), between the prologue and the solver's warm init: W = A X0
+// into h->d_ap on the path the solve's own products take, then R0 = B - W into h->d_r with B.B and R0.R0 per column
+// into h->d_warm (k_warm_residual, mspmv_warm.hip).  The workspace's partial rows are at least 2 L wide.
+static bool warm_start(const mspmv_handle_s *h) { return h->x0_mode == MSPMV_X0_CALLER; }
+static hipError_t launch_warm_start(mspmv_handle_s *h, const TilePlan &plan, const TilePlan *splan, const double *d_b,
+                                    const double *d_x, int L, int nblk)
+{
+    const hipError_t e = launch_solver_product(h, plan, splan, d_x, h->d_ap, L);
+    return e != hipSuccess ? e : launch_warm_residual(h, d_b, h->d_ap, h->d_r, L, nblk);
 }
 
 // Fills one of the handle's cached iteration graphs (GraphCache) for `key`: kept when it was captured with the
@@ -308,16 +328,20 @@ static mspmv_status cg_solve_native(mspmv_handle_s *h, const double *d_b, double
         *iters = 0;
     if (h->m == 0)
         return MSPMV_OK;
+    // A warm single-RHS solve runs the split iteration: the resident and pipelined kernels derive ||b|| from r.r
+    // inside their first iteration.  (cg_split_iteration's process-wide switch is the cold solves' alone.)
+    const bool warm = warm_start(h);
+    const bool split = cg_split_iteration(L) || warm;
     const TilePlan *plan = nullptr, *mplan = nullptr, *splan = nullptr;
     if (!hm && !ic) {
         // the split iteration's plain SpMM runs on the handle's offset-window or column-slab plan when
         // the plain product takes one, the pipelined single-RHS iteration's SpMV on its offset windows
         // (k_cg1_dia): decided here, before any graph capture (it may copy the matrix to the host)
         ST_TRY(product_plan(h, L, &splan));
-        if (!(splan->dia || (splan->slab && cg_split_iteration(L))))
+        if (!(splan->dia || (splan->slab && split)))
             splan = nullptr;
     }
-    if (splan && splan->dia && !cg_split_iteration(L))
+    if (splan && splan->dia && !split)
         plan = splan;  // the pipelined form on the windows needs no merge tiles
     else
         ST_TRY(solver_plan(h, L, &plan));
@@ -326,14 +350,15 @@ static mspmv_status cg_solve_native(mspmv_handle_s *h, const double *d_b, double
         ST_TRY(solver_plan(hm, L, &mplan));
         HIP_TRY(hipStreamSynchronize(hm->stream));  // hm's SpMMs are enqueued on h's stream
     }
-    const bool pipelined = !hm && !ic && !cg_split_iteration(L);  // single RHS: consumer-side reductions
+    const bool pipelined = !hm && !ic && !split;  // single RHS: consumer-side reductions
     bool stalled = false;
     const int nblk = pipelined ? cg1_blocks(h->m) : cg_update_blocks((long long)h->m * L, h->num_cus);
     const int cap = hist ? std::max(hist_cap, 0) : 0;
     // partials: one per tile of the plan, or per window of the offset-window plan (its dot mode)
     ST_TRY(ensure_cg_workspace(h, L, nblk,
                                std::max({plan->num_tiles, mplan ? mplan->num_tiles : 0, splan ? splan->num_tiles : 0}),
-                               cap));
+                               cap, 2 * L));  // (2 L: the warm start's pass -- cold solves too, so that a warm solve
+                                              // after a cold one keeps d_partials, which is in the graph's key)
     const int use_cap = hist ? cap : 0;
     if (pipelined) {
         // the whole solve as one register-resident launch, where the matrix fits (mspmv_cg_resident.hip)
@@ -366,21 +391,23 @@ static mspmv_status cg_solve_native(mspmv_handle_s *h, const double *d_b, double
     h->hist_cap = use_cap;  // kernels record only what the caller asked for
     int poison = 0;
     ST_TRY(solve_prologue(h, {plan, splan, mplan}, &poison));
+    if (warm)
+        HIP_TRY(launch_warm_start(h, *plan, splan, d_b, d_x, L, nblk));
     if (hm)
-        HIP_TRY(launch_pcg_init(h, hm, *mplan, d_b, d_x, L, tol, nblk));
+        HIP_TRY(launch_pcg_init(h, hm, *mplan, d_b, d_x, L, tol, nblk, warm));
     else if (ic)
-        HIP_TRY(launch_pcg_ic0_init(h, ic, d_b, d_x, L, tol, nblk));
+        HIP_TRY(launch_pcg_ic0_init(h, ic, d_b, d_x, L, tol, nblk, warm));
     else if (pipelined)
         HIP_TRY(launch_cg1_init(h, d_b, d_x, nblk));
     else
-        HIP_TRY(launch_cg_init(h, d_b, d_x, L, tol, nblk));
+        HIP_TRY(launch_cg_init(h, d_b, d_x, L, tol, nblk, warm));
     ST_TRY(solve_poison_fill(h, poison));  // (after the init's fold)
     auto iterate = [&](int i) -> hipError_t {
         if (hm)
             return launch_pcg_iteration(h, hm, *plan, *mplan, d_x, L, nblk, tol);
         if (ic)
             return launch_pcg_ic0_iteration(h, ic, *plan, d_x, L, nblk, tol);
-        return launch_cg_iteration(h, *plan, splan, dot_fused, d_x, L, i & 1, nblk, tol);
+        return launch_cg_iteration(h, *plan, splan, dot_fused, d_x, L, i & 1, nblk, tol, split);
     };
 
     const int K = cg_batch_iters(h->m, h->nnz, L);  // iterations per graph replay (even: p buffers alternate)
@@ -399,7 +426,8 @@ static mspmv_status cg_solve_native(mspmv_handle_s *h, const double *d_b, double
             reinterpret_cast<const void *>((intptr_t)use_cap), hm, mplan,
             hm ? (const void *)hm->d_vals : nullptr,
             reinterpret_cast<const void *>((uintptr_t)(hm ? hm->gen : 0)),
-            reinterpret_cast<const void *>((intptr_t)K), reinterpret_cast<const void *>((intptr_t)dot_fused)};
+            reinterpret_cast<const void *>((intptr_t)K), reinterpret_cast<const void *>((intptr_t)dot_fused),
+            reinterpret_cast<const void *>((intptr_t)split)};  // L = 1: the split and pipelined forms share cg_graph
         if (ic)
             tri_graph_key(ic, key);
         st = solver_graph(h, h->cg_graph, key, K, iterate, "CG");
@@ -485,6 +513,8 @@ static mspmv_status solve_dev_groups(mspmv_handle_s *h, const double *d_b, doubl
     for (int c0 = 0; c0 < L && st == MSPMV_OK;) {
         const int w = native_chunk(L - c0);
         hipError_t e = launch_panel_copy(d_b + c0, L, gb, w, (long long)m, w, w, h->stream);
+        if (e == hipSuccess && warm_start(h))  // the group's columns of X0, as B's
+            e = launch_panel_copy(d_x + c0, L, gx, w, (long long)m, w, w, h->stream);
         if (e != hipSuccess) {
             set_error(std::string("column group copy: ") + hipGetErrorString(e));
             st = MSPMV_ERR_HIP;
@@ -606,7 +636,10 @@ static mspmv_status bicgstab_solve_native(mspmv_handle_s *h, const double *d_b, 
     h->hist_cap = use_cap;  // kernels record only what the caller asked for
     int poison = 0;
     ST_TRY(solve_prologue(h, {plan, splan}, &poison));
-    HIP_TRY(launch_bicgstab_init(h, d_b, d_x, L, tol, nblk));
+    const bool warm = warm_start(h);
+    if (warm)
+        HIP_TRY(launch_warm_start(h, *plan, splan, d_b, d_x, L, nblk));
+    HIP_TRY(launch_bicgstab_init(h, d_b, d_x, L, tol, nblk, warm));
     ST_TRY(solve_poison_fill(h, poison));
     auto iterate = [&](int) -> hipError_t {
         if (ilu)
@@ -695,7 +728,7 @@ static mspmv_status bcg_solve_native(mspmv_handle_s *h, const double *d_b, doubl
     const int nblk = cg_update_blocks((long long)h->m * L, h->num_cus);
     const int cap = hist ? std::max(hist_cap, 0) : 0;
     // partial rows of the Gram folds are L^2 wide, one per block of the passes: the products take no partials
-    ST_TRY(ensure_cg_workspace(h, L, nblk, 0, cap, L * L));
+    ST_TRY(ensure_cg_workspace(h, L, nblk, 0, cap, std::max(L * L, 2 * L)));  // (2 L: the warm start's pass)
     if (!h->d_bcg)
         ST_TRY(dev_alloc(&h->d_bcg, (size_t)kBcgSmallDoubles));
     h->last_cg_kernel = "BlockCG-rQ (1 SpMM + 3 passes)";
@@ -705,7 +738,10 @@ static mspmv_status bcg_solve_native(mspmv_handle_s *h, const double *d_b, doubl
     h->hist_cap = use_cap;  // kernels record only what the caller asked for
     int poison = 0;
     ST_TRY(solve_prologue(h, {plan, splan}, &poison));
-    HIP_TRY(launch_bcg_init(h, d_b, d_x, L, tol, nblk));
+    const bool warm = warm_start(h);
+    if (warm)
+        HIP_TRY(launch_warm_start(h, *plan, splan, d_b, d_x, L, nblk));
+    HIP_TRY(launch_bcg_init(h, d_b, d_x, L, tol, nblk, warm));
     ST_TRY(solve_poison_fill(h, poison));
     auto iterate = [&](int) -> hipError_t { return launch_bcg_iteration(h, *plan, splan, d_x, L, nblk, tol); };
     const int K = cg_batch_iters(h->m, h->nnz, L);
@@ -731,7 +767,8 @@ static mspmv_status bcg_solve_native(mspmv_handle_s *h, const double *d_b, doubl
         const bool of_g = (fin.breakdown & kBcgBrokeG) != 0;
         set_error(std::string("block CG breakdown: pivot ") + std::to_string(fin.breakdown & 0xf) + " of " +
                   (of_g ? "G = S^T A S" : "H = V^T V") + " is <= 0 or non-finite " +
-                  (fin.iter == 0 && !of_g ? "at the init (a zero or dependent right-hand-side column)"
+                  (fin.iter == 0 && !of_g ? warm ? "at the init (a zero or dependent column of the initial residuals)"
+                                                  : "at the init (a zero or dependent right-hand-side column)"
                                           : "in iteration " + std::to_string(fin.iter - (of_g ? 0 : 1))) +
                   "; the block is rank deficient -- solve the columns independently with mspmv_dcg_multi");
         return MSPMV_ERR_BREAKDOWN;
@@ -739,8 +776,8 @@ static mspmv_status bcg_solve_native(mspmv_handle_s *h, const double *d_b, doubl
     return MSPMV_OK;
 }
 
-// Host-pointer form of a device solve: B up, solve_dev(dB, dX), X down (also after a breakdown: the other
-// columns were solved).
+// Host-pointer form of a device solve: B up (and X, the initial guess, on a warm-start handle), solve_dev(dB, dX),
+// X down (also after a breakdown: the other columns were solved).
 static mspmv_status solve_host(mspmv_handle h, const double *B, double *X, int L, int *iters,
                                const std::function<mspmv_status(const double *, double *)> &solve_dev)
 {
@@ -758,6 +795,10 @@ static mspmv_status solve_host(mspmv_handle h, const double *B, double *X, int L
     mspmv_status st = dev_alloc(&dX, (size_t)h->m * L);
     if (st == MSPMV_OK && hipMemcpy(dB, B, bytes, hipMemcpyHostToDevice) != hipSuccess) {
         set_error("B upload failed");
+        st = MSPMV_ERR_HIP;
+    }
+    if (st == MSPMV_OK && warm_start(h) && hipMemcpy(dX, X, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("X0 upload failed");
         st = MSPMV_ERR_HIP;
     }
     if (st == MSPMV_OK)
@@ -933,6 +974,148 @@ mspmv_status mspmv_dpcg_spai_multi(mspmv_handle a, mspmv_handle m, const double 
     (void)kernel;
     ST_TRY(check_handle(m));
     return cg_solve_host(a, B, X, L, max_iters, tolerance, iters, max_err_hist, hist_cap, m);
+}
+
+// ---- warm start and the fused true residual (mspmv_warm.hip) -------------------------------------
+mspmv_status mspmv_set_initial_guess(mspmv_handle h, int mode, int *old)
+{
+    if (mode != MSPMV_X0_ZERO && mode != MSPMV_X0_CALLER)
+        return invalid("set_initial_guess: unknown mode");
+    if (!h)
+        return invalid("null handle");
+    if (old)
+        *old = h->x0_mode;
+    h->x0_mode = mode;  // the inits run outside the cached iteration graphs: nothing to drop
+    return MSPMV_OK;
+}
+
+// One native-width panel: W = A X on the plain product's plan into h->d_resw (the one m x w panel this entry needs:
+// a handle never solved on allocates no solver workspace for it), then k_warm_residual; the 2 w sums to the host.
+// The pass's own tickets are zeroed first (a solve that stopped early may have left some raised) and a ticket fault
+// comes back in the control word.
+static mspmv_status residual_native(mspmv_handle_s *h, const double *d_B, const double *d_X, double *d_R, int w,
+                                    double *sums)
+{
+    const TilePlan *plan = nullptr;
+    ST_TRY(product_plan(h, w, &plan));
+    const int nblk = cg_update_blocks((long long)h->m * w, h->num_cus);
+    ST_TRY(ensure_fold_workspace(h, (size_t)nblk, 2 * w));
+    const size_t elems = (size_t)h->m * w;
+    if (elems > h->resw_cap) {
+        dev_free(h->d_resw);
+        h->resw_cap = 0;
+        ST_TRY(dev_alloc(&h->d_resw, elems));
+        h->resw_cap = elems;
+    }
+    HIP_TRY(hipMemsetAsync(h->d_ctrl, 0, sizeof(CgControl), h->stream));
+    HIP_TRY(hipMemsetAsync(h->d_gtickets, 0, sizeof(unsigned) * gtickets_capacity((size_t)nblk), h->stream));
+    int nk = 0;
+    HIP_TRY(launch_spmm(h, *plan, d_X, h->d_resw, w, &nk));
+    HIP_TRY(launch_warm_residual(h, d_B, h->d_resw, d_R, w, nblk));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(sums, h->d_warm, sizeof(double) * 2 * w, hipMemcpyDeviceToHost));
+    CgControl fin{};
+    HIP_TRY(hipMemcpy(&fin, h->d_ctrl, sizeof fin, hipMemcpyDeviceToHost));
+    if (fin.fault) {
+        set_error("residual: a reduction ticket drew past its group (the ticket array was not zero when the fold "
+                  "began): the norms are invalid");
+        return MSPMV_ERR_FAULT;
+    }
+    return MSPMV_OK;
+}
+
+mspmv_status mspmv_dresidual_dev(mspmv_handle h, const double *d_B, const double *d_X, double *d_R, int L,
+                                 double *norms)
+{
+    ST_TRY(check_handle(h));
+    if (L < 1)
+        return invalid("L must be >= 1");
+    if (!norms)
+        return invalid("residual: null norms");
+    if ((h->m > 0 && !d_B) || (h->m > 0 && h->n > 0 && !d_X))
+        return invalid("null vector");
+    for (int j = 0; j < 2 * L; ++j)
+        norms[j] = 0.0;
+    if (h->m == 0)
+        return MSPMV_OK;
+    double sums[32];
+    mspmv_status st = MSPMV_OK;
+    if (supported_L(L)) {
+        if (!aligned16(d_B) || !aligned16(d_X) || !aligned16(d_R))
+            return invalid("residual panels must be 16-byte aligned");
+        st = residual_native(h, d_B, d_X, d_R, L, sums);
+        for (int j = 0; st == MSPMV_OK && j < L; ++j) {
+            norms[j] = std::sqrt(sums[j]);
+            norms[L + j] = std::sqrt(sums[L + j]);
+        }
+    } else {
+        // column groups of native widths, each copied into contiguous panels (solve_dev_groups' way)
+        double *gb = nullptr, *gx = nullptr, *gr = nullptr;
+        ST_TRY(dev_alloc(&gb, (size_t)h->m * 16));
+        st = dev_alloc(&gx, (size_t)h->n * 16);
+        if (st == MSPMV_OK && d_R)
+            st = dev_alloc(&gr, (size_t)h->m * 16);
+        for (int c0 = 0; c0 < L && st == MSPMV_OK;) {
+            const int w = native_chunk(L - c0);
+            hipError_t e = launch_panel_copy(d_B + c0, L, gb, w, h->m, w, w, h->stream);
+            if (e == hipSuccess)
+                e = launch_panel_copy(d_X + c0, L, gx, w, h->n, w, w, h->stream);
+            if (e == hipSuccess)
+                st = residual_native(h, gb, gx, gr, w, sums);
+            if (e == hipSuccess && st == MSPMV_OK && d_R) {
+                e = launch_panel_copy(gr, w, d_R + c0, L, h->m, w, w, h->stream);
+                if (e == hipSuccess)
+                    e = hipStreamSynchronize(h->stream);
+            }
+            if (e != hipSuccess) {
+                set_error(std::string("residual column group: ") + hipGetErrorString(e));
+                st = MSPMV_ERR_HIP;
+            }
+            for (int j = 0; st == MSPMV_OK && j < w; ++j) {
+                norms[c0 + j] = std::sqrt(sums[j]);
+                norms[L + c0 + j] = std::sqrt(sums[w + j]);
+            }
+            c0 += w;
+        }
+        dev_free(gb);
+        dev_free(gx);
+        dev_free(gr);
+    }
+    if (st == MSPMV_OK)
+        st = mspmv_check_faults(h);  // the product's own tickets, as mspmv_dspmm
+    return st;
+}
+
+mspmv_status mspmv_dresidual(mspmv_handle h, const double *B, const double *X, double *R, int L, double *norms)
+{
+    ST_TRY(check_handle(h));
+    if (L < 1)
+        return invalid("L must be >= 1");
+    if (!norms)
+        return invalid("residual: null norms");
+    if ((h->m > 0 && !B) || (h->m > 0 && h->n > 0 && !X))
+        return invalid("null vector");
+    double *dB = nullptr, *dX = nullptr, *dR = nullptr;
+    const size_t mb = (size_t)h->m * L, nb = (size_t)h->n * L;
+    ST_TRY(dev_alloc(&dB, mb));
+    mspmv_status st = dev_alloc(&dX, nb);
+    if (st == MSPMV_OK && R)
+        st = dev_alloc(&dR, mb);
+    if (st == MSPMV_OK && (hipMemcpy(dB, B, sizeof(double) * mb, hipMemcpyHostToDevice) != hipSuccess ||
+                           hipMemcpy(dX, X, sizeof(double) * nb, hipMemcpyHostToDevice) != hipSuccess)) {
+        set_error("residual: upload failed");
+        st = MSPMV_ERR_HIP;
+    }
+    if (st == MSPMV_OK)
+        st = mspmv_dresidual_dev(h, dB, dX, dR, L, norms);
+    if (st == MSPMV_OK && R && hipMemcpy(R, dR, sizeof(double) * mb, hipMemcpyDeviceToHost) != hipSuccess) {
+        set_error("residual: download failed");
+        st = MSPMV_ERR_HIP;
+    }
+    dev_free(dB);
+    dev_free(dX);
+    dev_free(dR);
+    return st;
 }
 
 // ---- IC(0)-preconditioned CG (the factor: mspmv_tri.hip) ---------------------------------------

@@ -16,6 +16,7 @@ and every compute call goes through the HIP library.
 from __future__ import annotations
 
 import atexit
+import contextlib
 import ctypes
 import itertools
 import os
@@ -41,6 +42,7 @@ POISON_FILL, POISON_LATE_ZERO, POISON_NO_STOP = 1, 2, 4  # mspmv_test_poison_tic
 # frozen columns are reported, the others solved), so it is returned, not raised; everything
 # else -- STALL (8, an IC(0) triangular solve that never progressed) included -- raises.
 CACHE_AUTO, CACHE_STREAM, CACHE_RESIDENT = 0, 1, 2  # mspmv_set_cache_policy
+X0_ZERO, X0_CALLER = 0, 1  # mspmv_set_initial_guess
 SUPPORTED_L = (1, 2, 4, 8, 16)  # native tile-kernel widths; SpMM and the CGs take any L >= 1
 # (column chunks / groups of these widths; the sharded CG and the timing helpers native only)
 
@@ -120,6 +122,9 @@ _SIGS = {
     "mspmv_dspmm_dev": (_I, [_P, _P, _P, _I]),
     "mspmv_spmm_batch_dev": (_I, [_I, ctypes.POINTER(_P), ctypes.POINTER(_P), ctypes.POINTER(_P), _I]),
     "mspmv_sync_batch": (_I, [_I, ctypes.POINTER(_P)]),
+    "mspmv_set_initial_guess": (_I, [_P, _I, _PI]),
+    "mspmv_dresidual": (_I, [_P, _P, _P, _P, _I, _P]),
+    "mspmv_dresidual_dev": (_I, [_P, _P, _P, _P, _I, _P]),
     "mspmv_dcg_single": (_I, [_P, _P, _P, _I, _D, _PI, _P, _I]),
     "mspmv_dcg_single_dev": (_I, [_P, _P, _P, _I, _D, _PI, _P, _I]),
     "mspmv_cg_resident_stamps": (_I, [_P, _P, _P, _I, _D, _PI, _P, _I, _PI]),
@@ -270,6 +275,15 @@ def time_stream_read(device: int = 0, nbytes: int = 1 << 30, reps: int = 20) -> 
     g = ctypes.c_double(0.0)
     _check(lib.mspmv_time_stream_read(device, nbytes, reps, ctypes.byref(g)), "time_stream_read")
     return g.value
+
+
+def _x_start(B: np.ndarray, x0) -> np.ndarray:
+    """A host solver's X panel: uninitialised for a cold solve, a copy of the initial guess x0 (B's shape) for a
+    warm one."""
+    if x0 is None:
+        return np.empty_like(B)
+    X = np.array(x0, np.float64, order="C").reshape(B.shape)
+    return X
 
 
 def _ptr(a: np.ndarray) -> int:
@@ -577,6 +591,48 @@ class GpuCsr:
         (mspmv_set_cache_policy).  Synchronizes the handle and drops its cached solver graphs."""
         _check(lib.mspmv_set_cache_policy(self.h, int(policy)), "set_cache_policy")
 
+    def set_initial_guess(self, mode: int) -> int:
+        """X0_CALLER: every solver called with this matrix reads X on entry as its initial guess (warm start);
+        X0_ZERO (the default): x0 = 0.  Sticky on the handle (mspmv_set_initial_guess); returns the mode before."""
+        old = ctypes.c_int()
+        _check(lib.mspmv_set_initial_guess(self.h, int(mode), ctypes.byref(old)), "set_initial_guess")
+        return old.value
+
+    @contextlib.contextmanager
+    def _guess(self, warm: Optional[bool]):
+        """The handle's initial-guess mode for one call: X0_CALLER when `warm`, X0_ZERO when it is False, restored
+        after; None leaves the handle's own (sticky) mode in force."""
+        if warm is None:
+            yield
+            return
+        old = self.set_initial_guess(X0_CALLER if warm else X0_ZERO)
+        try:
+            yield
+        finally:
+            self.set_initial_guess(old)
+
+    def residual(self, B: np.ndarray, X: np.ndarray):
+        """(R, norms_B, norms_R): R = B - A X on the plain product with ||B_j|| and ||R_j|| per column from the
+        same pass (mspmv_dresidual); B [m] or [m, L], X [n] or [n, L], any L >= 1."""
+        B = np.ascontiguousarray(B, np.float64)
+        X = np.ascontiguousarray(X, np.float64)
+        flat = B.ndim == 1
+        B2, X2 = (B.reshape(-1, 1), X.reshape(-1, 1)) if flat else (B, X)
+        L = B2.shape[1]
+        assert B2.shape == (self.num_rows, L) and X2.shape == (self.num_cols, L)
+        R = np.empty_like(B2)
+        norms = np.zeros(2 * L, np.float64)
+        _check(lib.mspmv_dresidual(self.h, _ptr(B2), _ptr(X2), _ptr(R), L, _ptr(norms)), "dresidual")
+        return (R.reshape(-1) if flat else R), norms[:L].copy(), norms[L:].copy()
+
+    def residual_dev(self, dB: "DeviceBuffer", dX: "DeviceBuffer", dR: Optional["DeviceBuffer"], L: int):
+        """(norms_B, norms_R) of R = B - A X on device panels, R into dR unless it is None
+        (mspmv_dresidual_dev; synchronizes)."""
+        norms = np.zeros(2 * L, np.float64)
+        _check(lib.mspmv_dresidual_dev(self.h, dB.ptr, dX.ptr, dR.ptr if dR is not None else None, L, _ptr(norms)),
+               "dresidual_dev")
+        return norms[:L].copy(), norms[L:].copy()
+
     def cache_info(self):
         """(resident, bytes): whether the products read the matrix with default-policy loads, and what one plain
         single-RHS product streams from the matrix's arrays on its plan (mspmv_cache_info)."""
@@ -698,59 +754,68 @@ class GpuCsr:
         _check(lib.mspmv_last_kernel_ms(self.h, ctypes.byref(kms), ctypes.byref(kpc)), "last_kernel_ms")
         return ms.value, kms.value, kpc.value
 
-    def cg_single(self, b: np.ndarray, max_iters: int, tolerance: float, hist_cap: int = 0):
+    def cg_single(self, b: np.ndarray, max_iters: int, tolerance: float, hist_cap: int = 0, x0=None):
+        """x0 (every host solver's keyword): the initial guess, of B's shape -- the solve continues from it with the
+        stop test still relative to ||B|| (mspmv_set_initial_guess, for this call); None: x0 = 0."""
         b = np.ascontiguousarray(b, np.float64)
-        x = np.empty_like(b)
+        x = _x_start(b, x0)
         it = ctypes.c_int()
         hist = np.zeros(max(hist_cap, 1), np.float64)
-        st = lib.mspmv_dcg_single(self.h, _ptr(b), _ptr(x), max_iters, tolerance, ctypes.byref(it),
-                                  _ptr(hist) if hist_cap else None, hist_cap)
+        with self._guess(x0 is not None):
+            st = lib.mspmv_dcg_single(self.h, _ptr(b), _ptr(x), max_iters, tolerance, ctypes.byref(it),
+                                      _ptr(hist) if hist_cap else None, hist_cap)
         _check(st, "dcg_single", allow=(4,))
         return x, it.value, hist[: min(it.value, hist_cap)], st
 
     def cg_multi(self, B: np.ndarray, max_iters: int, tolerance: float, kernel: int = MERGE, hist_cap: int = 0,
-                 allow_fault: bool = False):
+                 allow_fault: bool = False, x0=None):
         B = np.ascontiguousarray(B, np.float64)
         L = B.shape[1]
-        X = np.empty_like(B)
+        X = _x_start(B, x0)
         it = ctypes.c_int()
         hist = np.zeros(max(hist_cap, 1), np.float64)
-        st = lib.mspmv_dcg_multi(self.h, _ptr(B), _ptr(X), L, max_iters, tolerance, kernel, ctypes.byref(it),
-                                 _ptr(hist) if hist_cap else None, hist_cap)
+        with self._guess(x0 is not None):
+            st = lib.mspmv_dcg_multi(self.h, _ptr(B), _ptr(X), L, max_iters, tolerance, kernel, ctypes.byref(it),
+                                     _ptr(hist) if hist_cap else None, hist_cap)
         _check(st, "dcg_multi", allow=(4, FAULT) if allow_fault else (4,))
         return X, it.value, hist[: min(it.value, hist_cap)], st
 
     def cg_dev(self, dB: DeviceBuffer, dX: DeviceBuffer, L: int, max_iters: int, tolerance: float,
-               hist_cap: int = 0):
+               hist_cap: int = 0, warm: Optional[bool] = None):
+        """warm (every *_dev solver's flag): True -- dX holds the initial guess on entry (mspmv_set_initial_guess,
+        for this call); False -- x0 = 0 for this call; None -- the mode set_initial_guess left on the handle."""
         it = ctypes.c_int()
         hist = np.zeros(max(hist_cap, 1), np.float64)
-        st = lib.mspmv_dcg_multi_dev(self.h, dB.ptr, dX.ptr, L, max_iters, tolerance, MERGE, ctypes.byref(it),
-                                     _ptr(hist) if hist_cap else None, hist_cap)
+        with self._guess(warm):
+            st = lib.mspmv_dcg_multi_dev(self.h, dB.ptr, dX.ptr, L, max_iters, tolerance, MERGE, ctypes.byref(it),
+                                         _ptr(hist) if hist_cap else None, hist_cap)
         _check(st, "dcg_multi_dev", allow=(4,))
         return it.value, hist[: min(it.value, hist_cap)], st
 
     def bicgstab(self, B: np.ndarray, max_iters: int, tolerance: float, hist_cap: int = 0,
-                 allow_fault: bool = False):
+                 allow_fault: bool = False, x0=None):
         """Multi-RHS BiCGSTAB for a square, possibly nonsymmetric matrix (mspmv_dbicgstab_multi):
         (X, iterations, history, status); a per-column breakdown is returned, not raised, as cg_multi's."""
         B = np.ascontiguousarray(B, np.float64)
         if B.ndim == 1:
             B = B.reshape(-1, 1)
         L = B.shape[1]
-        X = np.empty_like(B)
+        X = _x_start(B, x0)
         it = ctypes.c_int()
         hist = np.zeros(max(hist_cap, 1), np.float64)
-        st = lib.mspmv_dbicgstab_multi(self.h, _ptr(B), _ptr(X), L, max_iters, tolerance, ctypes.byref(it),
-                                       _ptr(hist) if hist_cap else None, hist_cap)
+        with self._guess(x0 is not None):
+            st = lib.mspmv_dbicgstab_multi(self.h, _ptr(B), _ptr(X), L, max_iters, tolerance, ctypes.byref(it),
+                                           _ptr(hist) if hist_cap else None, hist_cap)
         _check(st, "dbicgstab_multi", allow=(4, FAULT) if allow_fault else (4,))
         return X, it.value, hist[: min(it.value, hist_cap)], st
 
     def bicgstab_dev(self, dB: DeviceBuffer, dX: DeviceBuffer, L: int, max_iters: int, tolerance: float,
-                     hist_cap: int = 0):
+                     hist_cap: int = 0, warm: Optional[bool] = None):
         it = ctypes.c_int()
         hist = np.zeros(max(hist_cap, 1), np.float64)
-        st = lib.mspmv_dbicgstab_multi_dev(self.h, dB.ptr, dX.ptr, L, max_iters, tolerance, ctypes.byref(it),
-                                           _ptr(hist) if hist_cap else None, hist_cap)
+        with self._guess(warm):
+            st = lib.mspmv_dbicgstab_multi_dev(self.h, dB.ptr, dX.ptr, L, max_iters, tolerance, ctypes.byref(it),
+                                               _ptr(hist) if hist_cap else None, hist_cap)
         _check(st, "dbicgstab_multi_dev", allow=(4,))
         return it.value, hist[: min(it.value, hist_cap)], st
 
@@ -762,7 +827,7 @@ class GpuCsr:
         return nb.value, k.value
 
     def block_cg(self, B: np.ndarray, max_iters: int, tolerance: float, hist_cap: int = 0,
-                 allow_fault: bool = False):
+                 allow_fault: bool = False, x0=None):
         """Block CG (BCGrQ) for a symmetric positive definite matrix (mspmv_dbcg_multi): the columns share one
         Krylov space, so iterations fall as L grows.  (X, iterations, history, status); a breakdown (a rank-deficient
         block: MSPMV_ERR_BREAKDOWN, X the last completed iterate) is returned, not raised.  L in 1, 2, 4, 8, 16."""
@@ -770,43 +835,47 @@ class GpuCsr:
         if B.ndim == 1:
             B = B.reshape(-1, 1)
         L = B.shape[1]
-        X = np.empty_like(B)
+        X = _x_start(B, x0)
         it = ctypes.c_int()
         hist = np.zeros(max(hist_cap, 1), np.float64)
-        st = lib.mspmv_dbcg_multi(self.h, _ptr(B), _ptr(X), L, max_iters, tolerance, ctypes.byref(it),
-                                  _ptr(hist) if hist_cap else None, hist_cap)
+        with self._guess(x0 is not None):
+            st = lib.mspmv_dbcg_multi(self.h, _ptr(B), _ptr(X), L, max_iters, tolerance, ctypes.byref(it),
+                                      _ptr(hist) if hist_cap else None, hist_cap)
         _check(st, "dbcg_multi", allow=(4, FAULT) if allow_fault else (4,))
         return X, it.value, hist[: min(it.value, hist_cap)], st
 
     def block_cg_dev(self, dB: DeviceBuffer, dX: DeviceBuffer, L: int, max_iters: int, tolerance: float,
-                     hist_cap: int = 0):
+                     hist_cap: int = 0, warm: Optional[bool] = None):
         it = ctypes.c_int()
         hist = np.zeros(max(hist_cap, 1), np.float64)
-        st = lib.mspmv_dbcg_multi_dev(self.h, dB.ptr, dX.ptr, L, max_iters, tolerance, ctypes.byref(it),
-                                      _ptr(hist) if hist_cap else None, hist_cap)
+        with self._guess(warm):
+            st = lib.mspmv_dbcg_multi_dev(self.h, dB.ptr, dX.ptr, L, max_iters, tolerance, ctypes.byref(it),
+                                          _ptr(hist) if hist_cap else None, hist_cap)
         _check(st, "dbcg_multi_dev", allow=(4,))
         return it.value, hist[: min(it.value, hist_cap)], st
 
-    def pcg_spai(self, m: "GpuCsr", B: np.ndarray, max_iters: int, tolerance: float, hist_cap: int = 0):
+    def pcg_spai(self, m: "GpuCsr", B: np.ndarray, max_iters: int, tolerance: float, hist_cap: int = 0, x0=None):
         """SPAISolveMultiple with the preconditioner M's handle `m` (mspmv_dpcg_spai_multi)."""
         B = np.ascontiguousarray(B, np.float64)
         if B.ndim == 1:
             B = B[:, None]
         L = B.shape[1]
-        X = np.empty_like(B)
+        X = _x_start(B, x0)
         it = ctypes.c_int()
         hist = np.zeros(max(hist_cap, 1), np.float64)
-        st = lib.mspmv_dpcg_spai_multi(self.h, m.h, _ptr(B), _ptr(X), L, max_iters, tolerance, MERGE,
-                                       ctypes.byref(it), _ptr(hist) if hist_cap else None, hist_cap)
+        with self._guess(x0 is not None):
+            st = lib.mspmv_dpcg_spai_multi(self.h, m.h, _ptr(B), _ptr(X), L, max_iters, tolerance, MERGE,
+                                           ctypes.byref(it), _ptr(hist) if hist_cap else None, hist_cap)
         _check(st, "dpcg_spai_multi", allow=(4,))
         return X, it.value, hist[: min(it.value, hist_cap)], st
 
     def pcg_spai_dev(self, m: "GpuCsr", dB: DeviceBuffer, dX: DeviceBuffer, L: int, max_iters: int,
-                     tolerance: float, hist_cap: int = 0):
+                     tolerance: float, hist_cap: int = 0, warm: Optional[bool] = None):
         it = ctypes.c_int()
         hist = np.zeros(max(hist_cap, 1), np.float64)
-        st = lib.mspmv_dpcg_spai_multi_dev(self.h, m.h, dB.ptr, dX.ptr, L, max_iters, tolerance, MERGE,
-                                           ctypes.byref(it), _ptr(hist) if hist_cap else None, hist_cap)
+        with self._guess(warm):
+            st = lib.mspmv_dpcg_spai_multi_dev(self.h, m.h, dB.ptr, dX.ptr, L, max_iters, tolerance, MERGE,
+                                               ctypes.byref(it), _ptr(hist) if hist_cap else None, hist_cap)
         _check(st, "dpcg_spai_multi_dev", allow=(4,))
         return it.value, hist[: min(it.value, hist_cap)], st
 
@@ -960,17 +1029,18 @@ class GpuIc0(_GpuTriFactor):
         return self._solve(g, B, transpose)
 
 
-def pcg_ic0(g: "GpuCsr", ic: GpuIc0, B: np.ndarray, max_iters: int, tolerance: float, hist_cap: int = 0):
+def pcg_ic0(g: "GpuCsr", ic: GpuIc0, B: np.ndarray, max_iters: int, tolerance: float, hist_cap: int = 0, x0=None):
     """PCGSolveMultiple (mspmv_dpcg_ic0_multi): (X, iterations, history, status)."""
     B = np.ascontiguousarray(B, np.float64)
     if B.ndim == 1:
         B = B[:, None]
     L = B.shape[1]
-    X = np.empty_like(B)
+    X = _x_start(B, x0)
     it = ctypes.c_int()
     hist = np.zeros(max(hist_cap, 1), np.float64)
-    st = lib.mspmv_dpcg_ic0_multi(g.h, ic.h, _ptr(B), _ptr(X), L, max_iters, tolerance, MERGE, ctypes.byref(it),
-                                  _ptr(hist) if hist_cap else None, hist_cap)
+    with g._guess(x0 is not None):
+        st = lib.mspmv_dpcg_ic0_multi(g.h, ic.h, _ptr(B), _ptr(X), L, max_iters, tolerance, MERGE, ctypes.byref(it),
+                                      _ptr(hist) if hist_cap else None, hist_cap)
     _check(st, "dpcg_ic0_multi", allow=(4,))
     return X, it.value, hist[: min(it.value, hist_cap)], st
 
@@ -1038,29 +1108,31 @@ class GpuIlu0(_GpuTriFactor):
 
 
 def pbicgstab_ilu0(g: "GpuCsr", m: GpuIlu0, B: np.ndarray, max_iters: int, tolerance: float, hist_cap: int = 0,
-                   allow_fault: bool = False):
+                   allow_fault: bool = False, x0=None):
     """ILU(0)-preconditioned multi-RHS BiCGSTAB (mspmv_dpbicgstab_ilu0_multi): (X, iterations, history,
     status); a per-column breakdown is returned, not raised, as GpuCsr.bicgstab's."""
     B = np.ascontiguousarray(B, np.float64)
     if B.ndim == 1:
         B = B[:, None]
     L = B.shape[1]
-    X = np.empty_like(B)
+    X = _x_start(B, x0)
     it = ctypes.c_int()
     hist = np.zeros(max(hist_cap, 1), np.float64)
-    st = lib.mspmv_dpbicgstab_ilu0_multi(g.h, m.h, _ptr(B), _ptr(X), L, max_iters, tolerance, ctypes.byref(it),
-                                         _ptr(hist) if hist_cap else None, hist_cap)
+    with g._guess(x0 is not None):
+        st = lib.mspmv_dpbicgstab_ilu0_multi(g.h, m.h, _ptr(B), _ptr(X), L, max_iters, tolerance, ctypes.byref(it),
+                                             _ptr(hist) if hist_cap else None, hist_cap)
     _check(st, "dpbicgstab_ilu0_multi", allow=(4, FAULT) if allow_fault else (4,))
     return X, it.value, hist[: min(it.value, hist_cap)], st
 
 
 def pbicgstab_ilu0_dev(g: "GpuCsr", m: GpuIlu0, dB: DeviceBuffer, dX: DeviceBuffer, L: int, max_iters: int,
-                       tolerance: float, hist_cap: int = 0):
+                       tolerance: float, hist_cap: int = 0, warm: Optional[bool] = None):
     """mspmv_dpbicgstab_ilu0_multi_dev on device panels: (iterations, history, status)."""
     it = ctypes.c_int()
     hist = np.zeros(max(hist_cap, 1), np.float64)
-    st = lib.mspmv_dpbicgstab_ilu0_multi_dev(g.h, m.h, dB.ptr, dX.ptr, L, max_iters, tolerance, ctypes.byref(it),
-                                             _ptr(hist) if hist_cap else None, hist_cap)
+    with g._guess(warm):
+        st = lib.mspmv_dpbicgstab_ilu0_multi_dev(g.h, m.h, dB.ptr, dX.ptr, L, max_iters, tolerance,
+                                                 ctypes.byref(it), _ptr(hist) if hist_cap else None, hist_cap)
     _check(st, "dpbicgstab_ilu0_multi_dev", allow=(4,))
     return it.value, hist[: min(it.value, hist_cap)], st
 

@@ -60,6 +60,22 @@ int main()
         const int itm = CGSolveMultiple(a, B.data(), XS.data(), L, 5000, 1e-10, NONZERO_SPLIT, &errs);
         printf("CGSolveSingle %d iters, CGSolveMultiple %d iters (last max err %.3g)\n", it1, itm,
                errs.empty() ? -1.0 : errs.back());
+        // warm start: from the solutions just computed the columns are converged at entry (0 iterations, no history;
+        // 1 if a column's true residual sits a hair over the recurrence's); from a solution off by 1e-6 of itself
+        // (r0 = -1e-6 b: six of the ten decades done) fewer iterations than from zero
+        std::vector<double> e_warm;
+        const int itw0 = CGSolveMultiple(a, B.data(), XS.data(), L, 5000, 1e-10, NONZERO_SPLIT, from_x, &e_warm);
+        std::vector<double> near(sol);
+        for (double &v : near)
+            v *= 1.0 + 1e-6;
+        int itw1 = 0;
+        {
+            InitialGuess<CsrMatrix<double, int>> guess(a);
+            itw1 = CGSolveSingle(a, b.data(), near.data(), 5000, 1e-10);
+        }
+        const bool warm_ok = itw0 <= 1 && (int)e_warm.size() == itw0 && itw1 > 0 && itw1 < it1;
+        printf("warm start: CGSolveMultiple from its own solution %d iters, CGSolveSingle from (1 + 1e-6) x the solution %d "
+               "iters (cold %d)\n", itw0, itw1, it1);
         // num_vectors = 32: column chunks of the native widths over the same row-major panels
         const int L32 = 32;
         std::vector<double> X32((size_t)m * L32), Y32((size_t)m * L32), B32((size_t)m * L32), S32((size_t)m * L32);
@@ -106,7 +122,7 @@ int main()
         release(a);
         const bool ok32 = upd_ok && err32 < 1e-12 && itic > 0 && itsp > 0 && !e_ic.empty() && e_ic.back() < 1e-10 &&
                           !e_spai.empty() && e_spai.back() < 1e-10;
-        return (err < 1e-12 && it1 > 0 && itm > 0 && !errs.empty() && errs.back() < 1e-10 && ok32) ? 0 : 2;
+        return (warm_ok && err < 1e-12 && it1 > 0 && itm > 0 && !errs.empty() && errs.back() < 1e-10 && ok32) ? 0 : 2;
     } catch (const std::exception &e) {
         printf("error: %s\n", e.what());
         return 3;
