@@ -141,6 +141,26 @@ MSPMV_API mspmv_status mspmv_sync(mspmv_handle h);
  * queue of its own; a process has few).  Synchronizes the handle first. */
 MSPMV_API mspmv_status mspmv_set_cu_limit(mspmv_handle h, int num_cus);
 
+/* ---- Stream pool ------------------------------------------------------------------------ */
+/* Every device has a pool of four non-blocking streams, created back to back by the first mspmv_csr_create
+ * on it and never destroyed, so that each sits on a hardware queue of its own (a process opens four by
+ * default).  mspmv_csr_create{,_dev} leases the lowest free slot and runs the handle on that slot's stream;
+ * with every slot taken it creates a private stream, which shares a queue with some other.  The lease is
+ * exclusive and returned by mspmv_destroy, and by mspmv_set_cu_limit when it moves the handle to a CU-masked
+ * stream (back on all CUs the handle takes a free slot again, if there is one).  Independent products of a
+ * batch (mspmv_spmm_batch_dev) overlap fully only on distinct queues: keep at most four pooled handles per
+ * device alive where that matters.  MSPMV_STREAM_POOL=0 in the environment, read by every create, gives
+ * every handle a private stream as before the pool. */
+/* *slot = the pool slot whose stream h runs on (0..3), or -1: a private, caller's or CU-masked stream. */
+MSPMV_API mspmv_status mspmv_stream_slot(mspmv_handle h, int *slot);
+/* *slots = the slots of `device`'s pool, *leased = how many are held.  Either pointer may be NULL. */
+MSPMV_API mspmv_status mspmv_stream_pool_stats(int device, int *slots, int *leased);
+/* The slot ledger itself, host only (the handles' calls; exposed for tests): take puts the lowest free slot
+ * of `device` into *slot and holds it, or -1 with every slot held; give returns a held slot and refuses
+ * (MSPMV_ERR_INVALID) one that is not held.  Neither needs a device. */
+MSPMV_API mspmv_status mspmv_stream_slot_take(int device, int *slot);
+MSPMV_API mspmv_status mspmv_stream_slot_give(int device, int slot);
+
 /* ---- Infinity-Cache leases ------------------------------------------------------------ */
 /* Every product kernel exists in two forms: one reads the matrix's own arrays (values, columns,
  * records, panels) with default-policy loads, so their lines stay in the 256 MiB Infinity Cache for

@@ -5,6 +5,7 @@
 #include "mspmv_internal.h"
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -53,6 +54,59 @@ static mspmv_status check_offsets_host(const int *ro, int m, int nnz)
     return MSPMV_OK;
 }
 
+// ---- the stream pool: one stream per slot of the device's ledger (mspmv_streams.cpp) ----------
+// The four are created back to back on the first lease and never destroyed, not at unload either: created
+// together they sit on the process's four hardware queues, one each, and a handle that leases slot i always
+// runs on queue i.  Streams created one per handle, between uploads and plan builds, landed two on one queue
+// (DESIGN 4.2e).
+static std::mutex g_pool_mu;
+static std::map<int, std::array<hipStream_t, kStreamPool>> g_pool_streams;
+
+// MSPMV_STREAM_POOL, read per create: 0 = every handle creates a stream of its own, as before the pool.
+static bool stream_pool_env()
+{
+    const char *v = getenv("MSPMV_STREAM_POOL");
+    return !(v && v[0] == '0');
+}
+
+// The lowest free slot of `device` (the current device) and its stream; *slot stays -1, and *s untouched, with
+// the pool switched off or every slot taken.
+static mspmv_status pool_lease(int device, int *slot, hipStream_t *s)
+{
+    *slot = -1;
+    if (!stream_pool_env())
+        return MSPMV_OK;
+    std::lock_guard<std::mutex> lk(g_pool_mu);
+    auto it = g_pool_streams.find(device);
+    if (it == g_pool_streams.end()) {
+        std::array<hipStream_t, kStreamPool> a{};
+        for (int i = 0; i < kStreamPool; ++i)
+            if (hipStreamCreateWithFlags(&a[(size_t)i], hipStreamNonBlocking) != hipSuccess) {
+                while (i-- > 0)
+                    (void)hipStreamDestroy(a[(size_t)i]);
+                set_error("hipStreamCreate failed (stream pool)");
+                return MSPMV_ERR_HIP;
+            }
+        it = g_pool_streams.emplace(device, a).first;
+    }
+    ST_TRY(mspmv_stream_slot_take(device, slot));
+    if (*slot >= 0)
+        *s = it->second[(size_t)*slot];
+    return MSPMV_OK;
+}
+
+// The handle's stream goes: a private one is destroyed, a pool slot given back (a caller's or a CU-masked one
+// stays).  After the stream has been synchronised.
+static void release_stream(mspmv_handle_s *h)
+{
+    if (h->stream && h->own_stream)
+        (void)hipStreamDestroy(h->stream);
+    if (h->stream_slot >= 0)
+        (void)mspmv_stream_slot_give(h->device, h->stream_slot);
+    h->stream = nullptr;
+    h->stream_slot = -1;
+}
+
 // view_of: a row range of another handle on the same device -- a->row_offsets (host, rebased to 0)
 // are uploaded, the columns and values are the parent's from nonzero view_off on (not copied, not
 // owned; the parent validated them), a->column_indices / values are ignored.
@@ -92,14 +146,22 @@ static mspmv_status create_common(const mspmv_csr_d *a, int device, bool from_de
     if (hipDeviceGetAttribute(&h->num_cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess ||
         h->num_cus < 1)
         h->num_cus = 256;
+    mspmv_status st;
     if (on_stream) {  // a stream owned by the caller (mspmv_comm: one stream per rank)
         h->stream = on_stream;
         h->own_stream = false;
-    } else if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-        set_error("hipStreamCreate failed");
-        return fail(MSPMV_ERR_HIP);
+    } else {
+        // a slot of the device's pool, while there is one (a row-range view keeps a stream of its own making);
+        // before anything below submits work, so the pool's first use finds every hardware queue still free
+        if (!view_of && (st = pool_lease(device, &h->stream_slot, &h->stream)) != MSPMV_OK)
+            return fail(st);
+        if (h->stream_slot >= 0) {
+            h->own_stream = false;
+        } else if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
+            set_error("hipStreamCreate failed");
+            return fail(MSPMV_ERR_HIP);
+        }
     }
-    mspmv_status st;
     // Column / value arrays are padded (zero column index, zero value) so the kernels' aligned
     // 16-byte group reads past the last nonzero stay inside the allocation.
     const size_t padded = (size_t)h->nnz + kNnzPad;
@@ -356,8 +418,7 @@ mspmv_status mspmv_destroy(mspmv_handle h)
     if (h->ev1)
         (void)hipEventDestroy(h->ev1);
     resident_free(h->rcg);
-    if (h->stream && h->own_stream)
-        (void)hipStreamDestroy(h->stream);
+    release_stream(h);
     delete h;
     return MSPMV_OK;
 }
@@ -416,8 +477,15 @@ mspmv_status mspmv_set_cu_limit(mspmv_handle h, int num_cus)
     const int n = (num_cus <= 0 || num_cus >= total) ? total : num_cus;
     hipStream_t s = nullptr;
     bool own = true;
+    int slot = -1;
     if (n == total) {
-        HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        if (h->stream_slot >= 0)  // a pool stream runs on every CU already
+            return MSPMV_OK;
+        ST_TRY(pool_lease(h->device, &slot, &s));  // a free slot before a stream of its own
+        if (slot >= 0)
+            own = false;
+        else
+            HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     } else {
         std::lock_guard<std::mutex> lk(g_cu_mu);
         auto it = g_cu_streams.find({h->device, n});
@@ -440,6 +508,8 @@ mspmv_status mspmv_set_cu_limit(mspmv_handle h, int num_cus)
     if (e != hipSuccess) {
         if (own)
             (void)hipStreamDestroy(s);
+        if (slot >= 0)
+            (void)mspmv_stream_slot_give(h->device, slot);
         set_error(std::string("set_cu_limit: ") + hipGetErrorString(e));
         return MSPMV_ERR_HIP;
     }
@@ -448,10 +518,10 @@ mspmv_status mspmv_set_cu_limit(mspmv_handle h, int num_cus)
     h->bicg_graph.reset();
     h->pbicg_graph.reset();
     h->bcg_graph.reset();
-    if (h->own_stream)
-        (void)hipStreamDestroy(h->stream);
+    release_stream(h);
     h->stream = s;
     h->own_stream = own;
+    h->stream_slot = slot;
     if (n != h->num_cus) {
         // the register-resident CG layout is one workgroup per CU of the whole device: a CU-limited
         // stream cannot hold it (and one built while limited is "does not fit") -- rebuilt on demand
@@ -465,6 +535,15 @@ mspmv_status mspmv_set_cu_limit(mspmv_handle h, int num_cus)
         ST_TRY(solver_plan(h, 1, &plan));
         HIP_TRY(hipStreamSynchronize(h->stream));
     }
+    return MSPMV_OK;
+}
+
+mspmv_status mspmv_stream_slot(mspmv_handle h, int *slot)
+{
+    ST_TRY(check_handle(h));
+    if (!slot)
+        return invalid("stream_slot: null out pointer");
+    *slot = h->stream_slot;
     return MSPMV_OK;
 }
 

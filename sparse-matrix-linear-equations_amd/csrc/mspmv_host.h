@@ -1,5 +1,5 @@
 // mspmv_host.h -- what the host-only translation units (mspmv_ic0.cpp, mspmv_ilu0.cpp, mspmv_color.cpp,
-// mspmv_spai.cpp) share with each other and with the HIP ones (mspmv_internal.h includes it).  Needs no HIP.
+// mspmv_spai.cpp, mspmv_cache.cpp, mspmv_streams.cpp) share with each other and with the HIP ones (mspmv_internal.h includes it).  Needs no HIP.
 // Not installed; the public boundary is include/mspmv.h.
 #pragma once
 
@@ -17,6 +17,11 @@ inline mspmv_status invalid(const std::string &msg)
     set_error(msg);
     return MSPMV_ERR_INVALID;
 }
+
+// Slots of a device's stream pool (mspmv_streams.cpp keeps who holds which, mspmv_api.hip the streams): the
+// hardware queues a process opens by default, so that streams created back to back, one per slot, land each on
+// a queue of its own.  More streams than queues would only share them again.
+constexpr int kStreamPool = 4;
 
 // The structure of a host CSR: arrays present, row_offsets[0] == 0, offsets monotone and ending in num_nonzeros,
 // columns in [0, num_cols).  Else MSPMV_ERR_INVALID, the message prefixed with "who: ".  Squareness is the

@@ -314,7 +314,8 @@ struct mspmv_handle_s {
     int device = 0;
     int num_cus = 256;
     hipStream_t stream = nullptr;
-    bool own_stream = true;  // false: a shared CU-masked stream (mspmv_set_cu_limit)
+    bool own_stream = true;  // false: a shared CU-masked stream (mspmv_set_cu_limit), a caller's, or a pool slot's
+    int stream_slot = -1;    // the slot of the device's stream pool whose stream this is (mspmv_streams.cpp); -1: none
     bool own_arrays = true;  // false: d_cols / d_vals are a row range of another handle's (csr_create_view)
     int num_views = 0;       // row-range views cut from this handle (they read its d_vals: no value update)
     double update_ms = 0.0;  // wall ms of the last host-pointer mspmv_csr_update_values

@@ -115,6 +115,10 @@ _SIGS = {
     "mspmv_cache_floor": (_I, [_I, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]),
     "mspmv_cache_lease": (_I, [_I, ctypes.c_longlong, ctypes.c_longlong, _I, ctypes.POINTER(ctypes.c_longlong), _PI]),
     "mspmv_cache_leased": (_I, [_I, ctypes.POINTER(ctypes.c_longlong)]),
+    "mspmv_stream_slot": (_I, [_P, _PI]),
+    "mspmv_stream_pool_stats": (_I, [_I, _PI, _PI]),
+    "mspmv_stream_slot_take": (_I, [_I, _PI]),
+    "mspmv_stream_slot_give": (_I, [_I, _I]),
     "mspmv_merge_coords": (_I, [_P, _I, ctypes.POINTER(Coord)]),
     "mspmv_dspmv": (_I, [_P, _P, _P]),
     "mspmv_dspmv_dev": (_I, [_P, _P, _P]),
@@ -639,6 +643,14 @@ class GpuCsr:
         r, b = ctypes.c_int(), ctypes.c_longlong()
         _check(lib.mspmv_cache_info(self.h, ctypes.byref(r), ctypes.byref(b)), "cache_info")
         return bool(r.value), b.value
+
+    @property
+    def stream_slot(self) -> int:
+        """The slot of the device's stream pool whose stream this handle runs on, or -1: a private or CU-masked
+        stream (mspmv_stream_slot)."""
+        s = ctypes.c_int()
+        _check(lib.mspmv_stream_slot(self.h, ctypes.byref(s)), "stream_slot")
+        return s.value
 
     def merge_coords(self, num_parts: int) -> np.ndarray:
         out = (Coord * (num_parts + 1))()
@@ -1182,6 +1194,27 @@ def cache_leased(device: int = 0) -> int:
     b = ctypes.c_longlong()
     _check(lib.mspmv_cache_leased(device, ctypes.byref(b)), "cache_leased")
     return b.value
+
+
+def stream_pool_stats(device: int = 0):
+    """(slots, leased): the slots of the device's stream pool and how many a handle holds
+    (mspmv_stream_pool_stats; host only)."""
+    n, k = ctypes.c_int(), ctypes.c_int()
+    _check(lib.mspmv_stream_pool_stats(device, ctypes.byref(n), ctypes.byref(k)), "stream_pool_stats")
+    return n.value, k.value
+
+
+def stream_slot_take(device: int) -> int:
+    """The slot ledger's take, as a handle's create makes it (mspmv_stream_slot_take; host only): the lowest free
+    slot, now held, or -1 with every slot held."""
+    s = ctypes.c_int()
+    _check(lib.mspmv_stream_slot_take(device, ctypes.byref(s)), "stream_slot_take")
+    return s.value
+
+
+def stream_slot_give(device: int, slot: int) -> None:
+    """Returns a held slot (mspmv_stream_slot_give; host only); MspmvError for one that is not held."""
+    _check(lib.mspmv_stream_slot_give(device, int(slot)), "stream_slot_give")
 
 
 def block_record_encode(offsets) -> tuple:

@@ -7,6 +7,8 @@ The timed region of `bench.py --steps S` is the last 4 S launches of k_spmv_blk;
 belongs to matrix j (the sequence of handle j).  For each matrix's sequence: launches, mean duration,
 mean gap to the previous launch of the same sequence, and how many of its launches intersect a launch
 of each other sequence; plus queue / stream ids when the trace has them, and the region's span per launch.
+Then what paces the region: per Queue_Id the sequences it carries, its busy time and share of the region, per
+sequence the last end time, and the mean number of resident kernels (kernel time / span).
 """
 import csv
 import sys
@@ -39,6 +41,27 @@ def main():
             hit = sum(1 for s, e, _ in q if any(s < e2 and s2 < e for s2, e2, _ in seqs[k]))
             line += f"; intersects seq {k}: {hit}/{len(q)}"
         print(line)
+    # which queue paces the region: per Queue_Id the time a kernel of it is running (its own launches may
+    # overlap, so the union), each sequence's last end, and the region's mean number of resident kernels
+    span = t1 - t0
+    if "Queue_Id" in rows[0]:
+        byq = defaultdict(list)
+        for j in range(batch):
+            for s, e, r in seqs[j]:
+                byq[r["Queue_Id"]].append((s, e, j))
+        for qid in sorted(byq):
+            busy, hi = 0, t0
+            for s, e, _ in sorted(byq[qid]):
+                busy += max(0, e - max(s, hi))
+                hi = max(hi, e)
+            carried = sorted({j for _, _, j in byq[qid]})
+            print(f"queue {qid}: carries seq {carried}, {len(byq[qid])} launches, busy {busy / 1e3:.2f} us, "
+                  f"{100.0 * busy / span:.1f} % of the region")
+    ends = {j: max(e for _, e, _ in seqs[j]) for j in range(batch)}
+    for j in range(batch):
+        print(f"seq {j}: last end {(ends[j] - t0) / 1e3:.2f} us, {(t1 - ends[j]) / 1e3:.2f} us before the region's end")
+    total = sum(e - s for q in seqs.values() for s, e, _ in q)
+    print(f"mean resident kernels: {total / 1e3:.2f} us of kernel time / {span / 1e3:.2f} us span = {total / span:.2f}")
     # gaps between consecutive launches in dispatch order (the serial form: the launch boundary)
     allq = sorted((s, e) for q in seqs.values() for s, e, _ in q)
     gaps = [allq[i + 1][0] - allq[i][1] for i in range(len(allq) - 1)]
